@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — agent-steps/sec of one full MAPPO iteration (collect + GAE + PPO) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step, ...).  `--dump-outputs DIR` also writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs).  Everything else the benchmark measures runs only under `--full`: the extra objects listed below
+and, for N > 1, the weak-scaling companion.
 
 N > 1: one rank per GPU over RCCL.  Under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`,
 WORLD_SIZE set) this process is one of the ranks; started bare (`python bench.py --gpus N`) it spawns that launcher itself as a
@@ -14,7 +19,7 @@ simple_spread-shaped synthetic observations (obs 18, share_obs 54, Discrete(5)) 
 kernels writing into the HBM replay buffer, the bootstrap value + GAE scan, ppo_epoch=10 x num_mini_batch=1
 PPO updates (forward, fused loss, backward, [RCCL all-reduce], clip + Adam) and after_update.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  Extra objects (--full only; null otherwise):
   roofline     : the dominant kernel of the step — mlp_update16_dual_kernel: forward + PPO / value loss + backward of the
                  actor AND critic MLPs in one launch, bound by the fp32 MFMA rate; algorithmic flops 6*MACs/sample
                  (forward, dW, dX) / launch duration from HIP events attached to the dispatch.  `traffic` = HBM bytes per
@@ -138,11 +143,52 @@ def gae_roofline(runner, timer):
                 peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS)
 
 
+DUMP_MAX_ELEMS = 1 << 20       # per array; larger arrays are written as a fixed, seeded sample of their flattened elements
+DUMP_MAX_BYTES = 64 << 20      # all files together
+
+
+def dump_outputs(out_dir, runner, info):
+    """What the timed path hands its caller after the last timed step: train() statistics (train_info_<key>.npy, float64), the
+    parameters of both networks (actor.<key>.npy / critic.<key>.npy), the ValueNorm state and the replay buffer the rollout
+    filled (buffer.<name>.npy: env outputs, actions, log-probs, values, GAE returns, recurrent states).  float32 stays float32,
+    everything else becomes float64.  An array of more than DUMP_MAX_ELEMS elements is written as the elements at sorted indices
+    drawn by np.random.default_rng(0) from its flattened form (the same indices for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"train_info_{k}": torch.tensor(float(v), dtype=torch.float64) for k, v in sorted(info.items())}
+    pol = runner.trainer.policy
+    for tag, net in (("actor", pol.actor), ("critic", pol.critic)):
+        for k, v in net.state_dict().items():
+            arrays[f"{tag}.{k}"] = v
+    if runner.trainer.value_normalizer is not None:
+        arrays["value_normalizer.state"] = runner.trainer.value_normalizer.state
+    b = runner.buffer
+    for n in ("obs", "share_obs", "rnn_states", "rnn_states_critic", "value_preds", "returns", "actions", "action_log_probs",
+              "rewards", "masks", "bad_masks", "active_masks", "available_actions"):
+        if getattr(b, n, None) is not None:
+            arrays[f"buffer.{n}"] = getattr(b, n)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_MAX_ELEMS))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            t = flat
+        a = t.cpu().numpy()
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --config c4: 3)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; --config c4: 2)")
     ap.add_argument("--config", choices=("c2", "c4"), default="c2",
                     help="c2 = BASELINE configs[1], the configuration the metric is quoted on (default); c4 = configs[3], the SMAC MMM2 shape "
                          "(10 agents, obs 176 / state 322 / 18 actions, GRU policy, T=400, 512 rollout threads in total, ppo_epoch 5 x 2 "
@@ -158,6 +204,11 @@ def parse():
     ap.add_argument("--ppo_epoch", type=int, default=None)
     ap.add_argument("--num_mini_batch", type=int, default=None)
     ap.add_argument("--exact_minibatch_order", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: rooflines, per-kernel and per-phase device times, the "
+                         "CPU baseline and, for N > 1, the weak-scaling companion (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_companion", action="store_true", help="N > 1: skip the weak-scaling companion measurement")
     ap.add_argument("--cpu_threads", type=int, default=0, help="0 = all cores of this box (max 16)")
@@ -168,8 +219,10 @@ def parse():
     for k, v in zip(("n_rollout_threads", "episode_length", "ppo_epoch", "num_mini_batch"), dflt):
         if getattr(ns, k) is None:
             setattr(ns, k, v)
-    if ns.config == "c4" and ns.steps == 20 and ns.warmup == 3:
-        ns.steps, ns.warmup = 3, 2                            # an iteration is ~50 ms x 400 steps of rollout: keep the default run short
+    # c4: an iteration is ~50 ms x 400 steps of rollout: keep the default run short
+    for k, v in zip(("steps", "warmup"), dict(c2=(20, 3), c4=(3, 2))[ns.config]):
+        if getattr(ns, k) is None:
+            setattr(ns, k, v)
     return ns
 
 
@@ -322,6 +375,8 @@ def main_c4(ns, world, rank, device, result_out, force_dp):
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if ns.dump_outputs and rank == 0:
+        dump_outputs(ns.dump_outputs, runner, info)
     global_steps = a.episode_length * ns.global_threads * M
     out = dict(metric="agent-steps/sec (collect+GAE+PPO), SMAC MMM2-shaped synthetic env, recurrent policy", value=global_steps * ns.steps / dt,
                unit="agent-steps/s", n_gpus=world, steps=ns.steps, warmup=ns.warmup, ms_per_step=1e3 * dt / ns.steps, higher_is_better=True,
@@ -437,9 +492,11 @@ def main():
         env = SyntheticMPEEnv(args.n_rollout_threads, M, D, A, args.episode_length, seed=1 + rank, device=device)
     dp = DataParallel() if (world > 1 or force_dp) else None
     runner = MPERunner(dict(all_args=args, envs=env, eval_envs=None, num_agents=M, device=device, run_dir=None, dist_group=dp))
-    timer = KernelTimer()
-    install_timer(timer)
-    timer.reserve(4 * (args.episode_length + 4 * args.ppo_epoch * args.num_mini_batch + 8) + 64)
+    timer = None
+    if ns.full:                                            # the HIP-event hook serves only the --full measurements
+        timer = KernelTimer()
+        install_timer(timer)
+        timer.reserve(4 * (args.episode_length + 4 * args.ppo_epoch * args.num_mini_batch + 8) + 64)
 
     runner.warmup()
     for i in range(max(ns.warmup, 2)):                     # >= 2: eager pass, then hipGraph capture + first replay
@@ -462,6 +519,48 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if ns.dump_outputs and rank == 0:
+        dump_outputs(ns.dump_outputs, runner, info)       # before anything below runs the model again
+    per_gpu_steps = args.episode_length * args.n_rollout_threads * M      # this rank's share
+    global_steps = args.episode_length * ns.global_threads * M
+    value = global_steps * ns.steps / dt
+    out = dict(metric="agent-steps/sec (collect+GAE+PPO), MPE simple_spread 3-agent", value=value, unit="agent-steps/s",
+               n_gpus=world, steps=ns.steps, warmup=ns.warmup, ms_per_step=1e3 * dt / ns.steps, higher_is_better=True,
+               scaling=ns.scaling, vs_baseline=None, dtype="f32",
+               data="synthetic" if ns.env == "synthetic" else "MPE simple_spread dynamics on the GPU (mappo_amd/envs/mpe_spread.py), random-init weights",
+               config=dict(workload="BASELINE configs[1]: MPE simple_spread shape, 3 agents, obs 18 / share_obs 54 / Discrete(5), "
+                                    f"n_rollout_threads={ns.global_threads} in total ({ns.scaling} scaling: {args.n_rollout_threads} on rank 0 of "
+                                    f"{world}), episode_length={args.episode_length}, "
+                                    f"MLP policy (mappo), ppo_epoch={args.ppo_epoch}, num_mini_batch={args.num_mini_batch}, lr 7e-4, env={ns.env}",
+                           n_rollout_threads_global=ns.global_threads, n_rollout_threads_rank0=args.n_rollout_threads,
+                           episode_length=args.episode_length,
+                           num_agents=M, ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch,
+                           agent_steps_per_step=global_steps, parallelism=f"dp{world}", rccl_ranks=ns.rccl_ranks,
+                           exact_minibatch_order=bool(args.exact_minibatch_order), hip_graph=bool(runner.trainer._use_graph)),
+               roofline=None, ppo_loss_roofline=None, gae_roofline=None, kernels_us=None, phase_ms=None, weak_scaling_companion=None,
+               cpu_baseline=None, full=bool(ns.full),
+               last_train_info={k: float(v) for k, v in info.items()})
+    if ns.full:
+        full_measurements(ns, world, rank, device, args, runner, timer, dp, force_dp, out)
+    if rank == 0:
+        print(json.dumps(out), file=result_out, flush=True)
+    if world > 1 or force_dp:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(ns, world, rank, device, args, runner, timer, dp, force_dp, out):
+    """--full: everything beyond the headline figure, filled into `out` after the timed steps (same runner, same state)."""
+    from mappo_amd.envs.synthetic import SyntheticMPEEnv
+    from mappo_amd.runner.shared.mpe_runner import MPERunner
+    M, D, A = 3, 18, 5
+
+    def barrier():
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+        torch.cuda.synchronize()
 
     # ---- N > 1: the same K steps with the per-GPU work FIXED (weak scaling: configs[1]'s 1024 threads on EVERY rank) as a
     # companion figure — `value` above stays the strong-scaling number north_star asks for; a 1.3 ms iteration of ~50 dependent
@@ -472,6 +571,7 @@ def main():
         args_w = copy.copy(args)
         args_w.n_rollout_threads = ns.n_rollout_threads
         if ns.env == "mpe":
+            from mappo_amd.envs.mpe_spread import SimpleSpreadVecEnv
             env_w = SimpleSpreadVecEnv(args_w.n_rollout_threads, M, 3, args_w.episode_length, seed=101 + rank, device=device)
         else:
             env_w = SyntheticMPEEnv(args_w.n_rollout_threads, M, D, A, args_w.episode_length, seed=101 + rank, device=device)
@@ -521,8 +621,6 @@ def main():
     runner._use_graph, runner.trainer._use_graph = graph_flags
 
     per_gpu_steps = args.episode_length * args.n_rollout_threads * M      # this rank's share
-    global_steps = args.episode_length * ns.global_threads * M
-    value = global_steps * ns.steps / dt
     S = per_gpu_steps // args.num_mini_batch                 # samples per update-kernel launch
     H = 64
     macs_critic = D * M * H + H * H + H                     # forward MACs per sample (share_obs 54 -> 64 -> 64 -> 1)
@@ -548,36 +646,14 @@ def main():
                         traffic=None, flops_per_launch=flops, launch_us=us, note=note)
     loss_roof = ppo_loss_roofline(runner, timer, A)
     gae_roof = gae_roofline(runner, timer) if rank == 0 else None
-    out = dict(metric="agent-steps/sec (collect+GAE+PPO), MPE simple_spread 3-agent", value=value, unit="agent-steps/s",
-               n_gpus=world, steps=ns.steps, warmup=ns.warmup, ms_per_step=1e3 * dt / ns.steps, higher_is_better=True,
-               scaling=ns.scaling, vs_baseline=None, dtype="f32",
-               data="synthetic" if ns.env == "synthetic" else "MPE simple_spread dynamics on the GPU (mappo_amd/envs/mpe_spread.py), random-init weights",
-               config=dict(workload="BASELINE configs[1]: MPE simple_spread shape, 3 agents, obs 18 / share_obs 54 / Discrete(5), "
-                                    f"n_rollout_threads={ns.global_threads} in total ({ns.scaling} scaling: {args.n_rollout_threads} on rank 0 of "
-                                    f"{world}), episode_length={args.episode_length}, "
-                                    f"MLP policy (mappo), ppo_epoch={args.ppo_epoch}, num_mini_batch={args.num_mini_batch}, lr 7e-4, env={ns.env}",
-                           n_rollout_threads_global=ns.global_threads, n_rollout_threads_rank0=args.n_rollout_threads,
-                           episode_length=args.episode_length,
-                           num_agents=M, ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch,
-                           agent_steps_per_step=global_steps, parallelism=f"dp{world}", rccl_ranks=ns.rccl_ranks,
-                           exact_minibatch_order=bool(args.exact_minibatch_order), hip_graph=bool(graph_flags[1])),
-               roofline=roofline, ppo_loss_roofline=loss_roof, gae_roofline=gae_roof, kernels_us=kern, phase_ms=phase_ms,
-               weak_scaling_companion=companion,
-               last_train_info={k: float(v) for k, v in info.items()})
-    if rank == 0:
-        if world == 1 and not ns.no_cpu_baseline:
-            n_threads = ns.cpu_threads or min(os.cpu_count() or 1, 16)
-            try:
-                out["cpu_baseline"] = cpu_baseline(ns, n_threads)
-            except Exception as e:                             # the baseline must never take the GPU number down with it
-                out["cpu_baseline"] = dict(value=None, unit="agent-steps/s", cores=n_threads, kind="port", sample=f"failed: {e}")
-        else:
-            out["cpu_baseline"] = None
-        print(json.dumps(out), file=result_out, flush=True)
-    if world > 1 or force_dp:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    out.update(roofline=roofline, ppo_loss_roofline=loss_roof, gae_roofline=gae_roof, kernels_us=kern, phase_ms=phase_ms,
+               weak_scaling_companion=companion)
+    if rank == 0 and world == 1 and not ns.no_cpu_baseline:
+        n_threads = ns.cpu_threads or min(os.cpu_count() or 1, 16)
+        try:
+            out["cpu_baseline"] = cpu_baseline(ns, n_threads)
+        except Exception as e:                             # the baseline must never take the GPU number down with it
+            out["cpu_baseline"] = dict(value=None, unit="agent-steps/s", cores=n_threads, kind="port", sample=f"failed: {e}")
 
 
 if __name__ == "__main__":

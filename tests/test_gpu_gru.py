@@ -614,6 +614,37 @@ def test_config5_shape_train_vs_oracle_multi_tile(M):
     close(tr.value_normalizer.state, ovn.state(), 1e-5, 1e-7, "ValueNorm state")
 
 
+def _loss_kink_rows(oa, opol, ob, perms, tol=1e-4):
+    """Flat rows (t * R + r) of the oracle's buffer that are active and lie within `tol` of a non-smooth point of the PPO or
+    value loss (r_mappo.py:91-141) in ANY update of the oracle's train() with these permutations: the ratio at 1 -/+ clip_param,
+    |value - old value| at clip_param, the two value losses of the clipped value loss equal while the value is clipped.  Across
+    such a point the gradient jumps by one sample's worth, so fp32 on the GPU and fp32 on the CPU may differentiate two
+    different functions there, and Adam carries the difference into every later update.  Replays train_ref on a copy of
+    `opol` (the caller's policy and optimizers are untouched)."""
+    import copy
+    pol = copy.deepcopy(opol)
+    adv, _, _ = O.normalized_advantages_ref(ob.returns, ob.value_preds, ob.active_masks, None)
+    t = lambda x: torch.as_tensor(x, dtype=torch.float32)
+    c = oa.clip_param
+    loss = (lambda e: O.huber_ref(e, oa.huber_delta)) if oa.use_huber_loss else (lambda e: e ** 2 / 2)
+    near = set()
+    for e in range(oa.ppo_epoch):
+        for rows, h0 in O.recurrent_rows(ob.T, ob.N * ob.M, oa.num_mini_batch, oa.data_chunk_length, perms[e]):
+            sample = ob.sample(rows, O.adv_cast(adv, rows), h0)
+            share_obs, obs, rnn_a, rnn_c, actions, v_old, ret, masks, active, old_logp, _, avail = [t(x) for x in sample]
+            with torch.no_grad():
+                logp, _, _ = pol.actor.evaluate_actions(obs, rnn_a, actions, masks, avail, active)
+                values, _ = pol.critic(share_obs, rnn_c, masks)
+            imp = torch.exp(logp - old_logp)
+            d = values - v_old
+            gap = (loss(ret - values) - loss(ret - (v_old + d.clamp(-c, c)))).abs()
+            m = torch.minimum(torch.minimum((imp - (1 - c)).abs(), (imp - (1 + c)).abs()), (d.abs() - c).abs())
+            m = torch.where(d.abs() > c, torch.minimum(m, gap), m).view(-1).numpy()
+            near.update(int(r) for r in rows[(m < tol) & (active.view(-1).numpy() > 0)])
+            O.ppo_update_ref(oa, pol, None, sample)
+    return sorted(near)
+
+
 def test_config4_per_gpu_size_train_vs_oracle_on_active_subset(M):
     """BASELINE configs[3] at its PER-GPU size of an 8-GPU run (T=400, N=64 rollout threads, 10 agents, obs 176 / state 322 /
     18 actions, GRU, chunks of 10, num_mini_batch=2: 256 000 rows, 12 800 chunks per minibatch): wide-input trunk features,
@@ -658,6 +689,17 @@ def test_config4_per_gpu_size_train_vs_oracle_on_active_subset(M):
             part = np.concatenate([mapped[k * hs:(k + 1) * hs], inactive[k * (hf - hs):(k + 1) * (hf - hs)]])
             fp.append(rng.permutation(part))                                     # order inside a minibatch only reorders sums
         sub_perms.append(sp); full_perms.append(np.concatenate(fp))
+    # rows at a kink of the loss in some update are made inactive, in both buffers, until none is left (a row made inactive
+    # changes the denominators, hence the trajectory, hence which rows sit near a kink)
+    for _ in range(20):
+        near = _loss_kink_rows(oa, opol, ob, sub_perms)
+        if not near:
+            break
+        for row in near:
+            t_, r_ = divmod(row, len(keep) * Ma)
+            ob.active_masks[t_, r_ // Ma, r_ % Ma] = 0.0
+            buf.active_masks[t_, keep[r_ // Ma], r_ % Ma] = 0.0
+    assert not near, f"{len(near)} active rows still at a kink of the loss"
     oinfo = O.train_ref(oa, opol, None, ob, perms=sub_perms)
     it = iter(full_perms)
     buf._randperm = lambda n: torch.from_numpy(next(it)).to(buf.device)          # the permutation stream of recurrent_rows

@@ -487,6 +487,28 @@ def _relu_margin(net, x):
     return torch.stack(margins).min(dim=0).values.numpy()
 
 
+def _loss_margin(a, actor, critic, obs, sobs, actions, avail, active, old_logp, v_old, ret, vn):
+    """Distance per row (float64 oracle networks) to the non-smooth points of the PPO and value losses (r_mappo.py:91-141): the
+    ratio at 1 -/+ clip_param, |value - old value| at clip_param, and the two Huber losses of the clipped value loss equal while
+    the value is clipped.  The gradient jumps by one sample's worth across each of them."""
+    import copy
+    t = lambda x: torch.from_numpy(x).double()
+    ad, cd = copy.deepcopy(actor).double(), copy.deepcopy(critic).double()
+    with torch.no_grad():
+        lp, _, _ = ad.evaluate_actions(t(obs), None, t(actions).view(-1, 1), None, t(avail), t(active).view(-1, 1))
+        vals = cd(t(sobs), None, None)[0]
+    c = a.clip_param
+    imp = torch.exp(lp - t(old_logp).view(-1, 1))
+    m_ratio = torch.minimum((imp - (1 - c)).abs(), (imp - (1 + c)).abs())
+    vo = t(v_old).view(-1, 1)
+    d = vals - vo
+    tgt = vn.normalize(t(ret).view(-1, 1)).double()
+    vclip = vo + d.clamp(-c, c)
+    gap = (O.huber_ref(tgt - vals, a.huber_delta) - O.huber_ref(tgt - vclip, a.huber_delta)).abs()
+    m_max = torch.where(d.abs() > c, gap, torch.full_like(gap, np.inf))
+    return torch.minimum(torch.minimum(m_ratio, (d.abs() - c).abs()), m_max).view(-1).numpy()
+
+
 @pytest.mark.parametrize("D,S,A,relu,B,with_rows", [(18, 54, 5, True, 3072, True), (18, 54, 5, False, 500, False),
                                                     (30, 48, 9, True, 333, True), (64, 64, 18, True, 100, False),
                                                     (18, 54, 5, True, 76800, False), (176, 322, 18, True, 700, True),
@@ -535,6 +557,11 @@ def test_fused_update_kernels_vs_unfused_and_autograd(ops, D, S, A, relu, B, wit
         v_now = critic(torch.from_numpy(sobs), None, None)[0].numpy().reshape(-1)
     v_old = (v_now + rng.standard_normal(n_rows) * 0.25).astype(f)
     vn = O.ValueNormRef(); vn.update(ret[:50].reshape(-1, 1)); vn.update(ret[rows].reshape(-1, 1))
+    if B > 4000 and D > 64:
+        # the same for the loss's own kinks (ratio clip, value clip, max of the two value losses): a row within 1e-4 of one
+        # may take the other branch in fp32 than in the float64 reference below (measured: one such row moves the critic
+        # gradient by 2e-4 of its largest entry at B = 47 019)
+        active[_loss_margin(a, actor, critic, obs, sobs, actions, avail, active, old_logp, v_old, ret, vn) < 1e-4] = 0.0
     d_rows = dev(rows, torch.int32) if with_rows else None
     g = dict(obs=dev(obs), sobs=dev(sobs), avail=dev(avail), actions=dev(actions), old=dev(old_logp), adv=dev(adv),
              active=dev(active), ret=dev(ret), vold=dev(v_old), vn=dev(vn.state()))
