@@ -195,6 +195,22 @@ int mappo_rollout_step(const float *actor_params, const mappo_net_desc *actor_de
                        float *values /*[B]*/, float *obs_dst /*or NULL: no insert*/, float *share_dst, const float *rewards,
                        int64_t rew_stride_n, int64_t rew_stride_m, const uint8_t *dones, int64_t done_stride_n,
                        int64_t done_stride_m, float *rew_dst, float *mask_dst, int32_t centralized, mappo_stream_t stream);
+/* One launch per rollout EPISODE, for envs whose output for the whole episode exists before it starts and does not depend on
+ * the actions (synthetic MPE): what T + 1 mappo_rollout_step calls do, with the env output of step t at
+ * env_obs[t*obs_stride_t + n*obs_stride_n + m*obs_stride_m + d], rewards / dones likewise (bool bytes).  Actor on the rows of
+ * step t < T (step 0: obs_buf slot 0, step t >= 1: the env output of step t - 1 in place) with counter + t (+ *counter_dev)
+ * -> actions / logp [T][B]; critic on the share rows of step t <= T -> values [T][B], step T -> next_values [B]; the env output
+ * of step t is copied into obs_buf / share_buf slot t + 1 ([T+1][B][in_dim]), rew_buf [T][B] slot t and mask_buf [T+1][B]
+ * slot t + 1.  B = N*M rows; networks with in_dim <= 64 that share layer_N and the activation; not recurrent; no available
+ * actions.  centralized: the critic's row of (n, m) is the thread's M agent rows side by side (obs_stride_m == in_dim). */
+int mappo_rollout_episode(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *critic_params,
+                          const mappo_net_desc *critic_desc /*host*/, int32_t T, int32_t N, int32_t M, const float *env_obs,
+                          int64_t obs_stride_t, int64_t obs_stride_n, int64_t obs_stride_m, const float *rewards,
+                          int64_t rew_stride_t, int64_t rew_stride_n, int64_t rew_stride_m, const uint8_t *dones,
+                          int64_t done_stride_t, int64_t done_stride_n, int64_t done_stride_m, int32_t deterministic,
+                          uint64_t seed, uint64_t counter, const uint64_t *counter_dev, float *obs_buf, float *share_buf,
+                          float *rew_buf, float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/,
+                          float *values /*[T][B]*/, float *next_values /*[B]*/, int32_t centralized, mappo_stream_t stream);
 int32_t mappo_mlp_backward_slabs(int64_t B); /* number of slabs the launch below will write */
 int mappo_mlp_backward(const float *params, const mappo_net_desc *desc /*host*/, const float *x,
                        const int32_t *rows, int64_t B, const float *dout /*[B][out_dim]*/,

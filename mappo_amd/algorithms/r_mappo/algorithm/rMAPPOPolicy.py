@@ -191,6 +191,32 @@ class R_MAPPOPolicy:
                          buffer.action_log_probs[step].view(R), buffer.value_preds[step].view(R), insert)
         return buffer.actions[step]
 
+    def can_fuse_episode(self):
+        """mappo_rollout_episode covers the narrow networks of the stepwise kernel (in_dim <= 64), not recurrent."""
+        return self.can_fuse_step() and max(self.actor.desc.in_dim, self.critic.desc.in_dim) <= 64
+
+    @torch.no_grad()
+    def collect_episode_fused(self, buffer, block, next_values, centralized=True, deterministic=False):
+        """A whole rollout episode in one launch (mappo_rollout_episode): `block` = (obs [T, N, M, D], rewards, dones) — the env
+        output of every step, handed out before the episode (SyntheticMPEEnv.episode_block).  Writes what T x collect_step_fused
+        + the bootstrap call write: buffer.{actions, action_log_probs, value_preds}[0..T-1], the inserts into obs / share_obs /
+        masks [1..T] and rewards [0..T-1], and the critic of step T into `next_values` [N*M].  Step t samples with counter
+        t + *_counter_dev, as the stepwise path does."""
+        obs, rewards, dones = block
+        b = buffer
+        T, N, M = b.episode_length, b.n_rollout_threads, b.num_agents
+        D = self.actor.desc.in_dim
+        ok = (torch.is_tensor(obs) and obs.device == self.device and obs.dtype == torch.float32 and tuple(obs.shape) == (T, N, M, D)
+              and obs.stride(3) == 1 and torch.is_tensor(rewards) and rewards.device == self.device and rewards.dtype == torch.float32
+              and torch.is_tensor(dones) and dones.device == self.device and dones.dtype == torch.bool
+              and all(t.is_contiguous() for t in (b.obs, b.share_obs, b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds)))
+        if not ok:
+            raise ValueError("collect_episode_fused: the episode block / buffer do not have the device layout mappo_rollout_episode reads")
+        ops.rollout_episode(self.actor.flat, self.actor.desc, self.critic.flat, self.critic.desc, obs, rewards, dones, deterministic,
+                            self.actor._seed, 0, self.actor._counter_dev, b.obs, b.share_obs, b.rewards, b.masks, b.actions,
+                            b.action_log_probs, b.value_preds, next_values, centralized)
+        return next_values
+
     # ---- recurrent policies, SMAC-style envs: insert of the previous env output + this step's get_actions in one launch ----
     def can_fuse_recurrent_step(self, n_rows):
         from mappo_amd import recurrent

@@ -96,6 +96,10 @@ def get_config():
     p.add_argument("--fuse_rollout_step", **off,
                    help="by default an MLP policy's rollout step (insert of the previous env output + get_actions + get_values) "
                         "is ONE kernel launch (mappo_rollout_step); pass the flag to use the separate insert / actor / critic launches")
+    p.add_argument("--fuse_rollout_episode", **off,
+                   help="by default, with an env that hands out a whole episode up front (SyntheticMPEEnv.episode_block) and a "
+                        "narrow MLP policy, the rollout episode (T x get_actions, T + 1 x get_values, every insert) is ONE kernel "
+                        "launch (mappo_rollout_episode); pass the flag to run the stepwise loop")
     p.add_argument("--dual_update", **off,
                    help="by default the actor's and the critic's fused update run in ONE launch, half the CUs each "
                         "(mappo_actor_critic_update); pass the flag to launch them one after the other")

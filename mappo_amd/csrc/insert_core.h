@@ -29,6 +29,57 @@ __device__ __forceinline__ void insert_mpe_body(const InsertArgs &p, int bid, in
   }
 }
 
+// The MPE insert of a whole episode (rollout_episode_kernel): p describes step 0 (sources: the env output of step 0, destinations:
+// the buffer slots it goes to); step t reads the sources t * *_st further and writes t slots further.  Flattened over (step,
+// element), U elements per lane per pass with every load of a pass issued before its stores: one dependent round trip per
+// element (insert_mpe_body's loop) made this role the long pole of the launch.
+template <int U>
+__device__ __forceinline__ void insert_mpe_episode_body(const InsertArgs &p, int64_t obs_st, int64_t rew_st, int64_t done_st, int T,
+                                                        int bid, int nb) {
+  const int S = p.centralized ? p.M * p.D : p.D;
+  const int64_t R = (int64_t)p.N * p.M, RS = R * S, total = (int64_t)T * RS, nthr = (int64_t)nb * blockDim.x;
+  for (int64_t e0 = (int64_t)bid * blockDim.x + threadIdx.x; e0 < total; e0 += U * nthr) {
+    float v[U], rw[U];
+    uint8_t dn[U];                                   // raw: a compare here would wait for the load (and every load before it)
+    int64_t tn[U];                                   // t * R + nm: the row's index in the [T][R] slots
+    int dd[U], jj[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e = e0 + u * nthr;
+      jj[u] = -1;
+      if (e < total) {
+        const int64_t t = e / RS, rem = e - t * RS, nm = rem / S;
+        const int j = (int)(rem - nm * S);
+        const int n = (int)(nm / p.M), m = (int)(nm - (int64_t)n * p.M);
+        const int ms = p.centralized ? j / p.D : m, d = p.centralized ? j - ms * p.D : j;      // source agent / feature
+        v[u] = p.obs[t * obs_st + n * p.obs_sn + ms * p.obs_sm + d];
+        tn[u] = t * R + nm;
+        dd[u] = (!p.centralized || ms == m) ? d : -1;                                        // each obs element exactly once
+        jj[u] = j;
+        if (j == 0) {
+          rw[u] = p.rew[t * rew_st + n * p.rew_sn + m * p.rew_sm];
+          dn[u] = p.done[t * done_st + n * p.done_sn + m * p.done_sm];
+        }
+      }
+    }
+    // one wait for the whole pass: the stores sit in divergent branches, where the counter's bookkeeping otherwise falls back to
+    // a full wait (loads AND the stores before) in front of every group of stores
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (jj[u] < 0) continue;
+      p.share_dst[e0 + u * nthr] = v[u];                                                     // share slots t + 1 are contiguous
+      if (dd[u] >= 0) p.obs_dst[tn[u] * p.D + dd[u]] = v[u];
+      if (jj[u] == 0) {
+        p.rew_dst[tn[u]] = rw[u];
+        p.mask_dst[tn[u]] = dn[u] != 0 ? 0.f : 1.f;
+      }
+    }
+  }
+}
+
 // ---- the SMAC rollout insert (insert.hip: mappo_insert_smac) as a device function, shared with the fused recurrent rollout step ----
 struct SmacInsert {
   const float *obs, *share, *avail;              // contiguous [N*M][D | S | A]

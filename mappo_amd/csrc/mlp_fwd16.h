@@ -138,6 +138,99 @@ __device__ __forceinline__ void forward16_tail(const FwdArgs &p, float *lds, con
 // no LDS except the logits tile of the sampling epilogue.  k-step (b, i) takes input / hidden feature 16 b + 4 q + i in every
 // layer.  (Rows of W1 are read up to 15 floats past in_dim — into the next row or the bias that follows W1 in the flat
 // parameter vector: finite values that meet zero inputs.)
+// head rows of lane (j, q) (MODE 0: block 0 only — the critic's row 0; MODE 1: two blocks of 16 actions; MODE 2: none)
+template <int MODE>
+struct Head16R {
+  static constexpr int NBH = MODE == 1 ? 2 : (MODE == 0 ? 1 : 0);     // head blocks of 16 outputs
+  f32x4 wh[NBH > 0 ? NBH : 1][4];
+  f32x4 bhv[NBH > 0 ? NBH : 1];
+};
+template <int MODE>
+__device__ __forceinline__ void head16r_load(Head16R<MODE> &hd, const float *P, const NetOff &o, int A, int j, int q) {
+  if constexpr (Head16R<MODE>::NBH > 0) {
+#pragma unroll
+    for (int bo = 0; bo < Head16R<MODE>::NBH; ++bo) {
+      const int a = 16 * bo + j;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        // rows beyond A: a repeat of the last row (clamped index) — their logits are never stored, and a select here would be
+        // an instruction on a value in flight (see trunk16r_load)
+        hd.wh[bo][b] = ld4ua(P + o.wh + (size_t)min(a, A - 1) * HID + 16 * b + 4 * q);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hd.bhv[bo][r] = P[o.bh + min(16 * bo + 4 * q + r, A - 1)];
+    }
+  }
+}
+
+// The per-tile step of the register-resident forward: trunk, head, and the tile's outputs (MODE 0: out[i] = value;
+// MODE 1: sample / argmax with counter ctr_base (+ *ctr_dev) -> actions[i], logp[i]; MODE 2: trunk output out[64][B]).
+// x: the lane's raw input features (see trunk16r_apply).  Shared by the stepwise kernels and the episode kernel, so a row's
+// results do not depend on which launch computes them.  DRAIN (episode kernel): wait for every load in flight — the next step's
+// rows, requested before this step's math — in front of the stores.  The stores sit in a divergent branch, so behind them the
+// counter can only be drained whole: the next step's wait for its rows would also wait for this step's stores to complete.
+template <bool RELU, int LN, int MODE, bool DRAIN = false>
+__device__ __forceinline__ void tile16r_step(const FwdArgs &p, const Trunk16R<LN> &tw, const Head16R<MODE> &hd, f32x4 (&x)[4],
+                                             float *out, float *actions, float *logp, uint64_t ctr_base, const uint64_t *ctr_dev,
+                                             float *tZ, const int64_t i, const bool ok, const int j, const int q) {
+  constexpr int NBH = Head16R<MODE>::NBH;
+  const int D = p.desc.in_dim, A = p.desc.out_dim;
+  const bool fnorm = p.desc.use_feature_norm != 0;
+  f32x4 h[4];
+  trunk16r_apply<RELU, LN>(tw, x, h, D, ok, fnorm, q);
+  // ---- head ----
+  if constexpr (MODE == 2) {
+    if (ok) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[(int64_t)(16 * b + 4 * q + r) * p.B + i] = h[b][r];
+    }
+  } else {
+    f32x4 z[NBH > 0 ? NBH : 1];
+#pragma unroll
+    for (int bo = 0; bo < NBH; ++bo) {
+      z[bo] = hd.bhv[bo];
+      if (bo == 0 || A > 16) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) z[bo] = mfma16(hd.wh[bo][b][r], h[b][r], z[bo]);
+      }
+    }
+    if constexpr (DRAIN) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); }
+    if constexpr (MODE == 0) {
+      if (A == 1) { if (ok && q == 0) out[i] = z[0][0]; }
+      else if (ok) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const int a = 4 * q + r; if (a < A) out[i * A + a] = z[0][r]; }     // (out_dim <= 16 through this path)
+      }
+    } else {
+#pragma unroll
+      for (int bo = 0; bo < NBH; ++bo)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const int a = 16 * bo + 4 * q + r; if (a < A) tZ[j * TP + a] = z[bo][r]; }
+      wave_lds_sync();
+      if (ok && q == 0) {
+        const uint64_t ctr = ctr_base + (ctr_dev ? *ctr_dev : 0ull);
+        float action, lp;
+        categorical_act_lane(tZ + j * TP, A, p.avail ? p.avail + i * A : nullptr, p.deterministic != 0, p.seed, ctr, (uint64_t)i, action, lp);
+        actions[i] = action;
+        logp[i] = lp;
+      }
+      wave_lds_sync();
+    }
+  }
+}
+
+// ---- the same forward with the weights in REGISTERS -------------------------------------------------------------------------
+// A rollout-sized launch is one tile per wave: staging the weights through LDS (global -> registers -> LDS -> barrier -> scalar
+// operand reads) is then most of the launch.  Here every wave loads its A operands straight from global memory as 16-byte loads
+// (W1, W2.., head: <= 200 registers; the waves of a workgroup fetch the same lines, so L1 / L2 serve all but the first), along
+// with the per-feature vectors it needs as 4-wide registers, ALL issued before anything waits: one memory latency, no barrier,
+// no LDS except the logits tile of the sampling epilogue.  k-step (b, i) takes input / hidden feature 16 b + 4 q + i in every
+// layer.  (Rows of W1 are read up to 15 floats past in_dim — into the next row or the bias that follows W1 in the flat
+// parameter vector: finite values that meet zero inputs.)
 template <bool RELU, int LN, int MODE>
 __device__ __forceinline__ void forward16r_body(const FwdArgs &p, float *lds, const int bid, const int nb) {
   const int n_waves = blockDim.x / WAVE;
@@ -145,7 +238,6 @@ __device__ __forceinline__ void forward16r_body(const FwdArgs &p, float *lds, co
   const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), j = lane & 15, q = lane >> 4;
   const int D = p.desc.in_dim, A = p.desc.out_dim;
   const int64_t n_tiles = (p.B + 15) / 16;
-  const bool fnorm = p.desc.use_feature_norm != 0;
   float *tZ = lds + wave * 16 * TP;                              // [16][TP] logits of this wave's samples (MODE 1)
   int64_t tile = (int64_t)bid * n_waves + wave;
   if (tile >= n_tiles) return;
@@ -167,23 +259,8 @@ __device__ __forceinline__ void forward16r_body(const FwdArgs &p, float *lds, co
   // ---- weights and vectors of this lane (issued before the first wait) ----
   Trunk16R<LN> tw;
   trunk16r_load<LN>(tw, P, o, p.desc, j, q);
-  constexpr int NBH = MODE == 1 ? 2 : (MODE == 0 ? 1 : 0);       // head blocks of 16 outputs (critic: row 0 only)
-  f32x4 wh[NBH > 0 ? NBH : 1][4];
-  f32x4 bhv[NBH > 0 ? NBH : 1];
-  if constexpr (NBH > 0) {
-#pragma unroll
-    for (int bo = 0; bo < NBH; ++bo) {
-      const int a = 16 * bo + j;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        // rows beyond A: a repeat of the last row (clamped index) — their logits are never stored, and a select here would be
-        // an instruction on a value in flight (see trunk16r_load)
-        wh[bo][b] = ld4ua(P + o.wh + (size_t)min(a, A - 1) * HID + 16 * b + 4 * q);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bhv[bo][r] = P[o.bh + min(16 * bo + 4 * q + r, A - 1)];
-    }
-  }
+  Head16R<MODE> hd;
+  head16r_load<MODE>(hd, P, o, A, j, q);
   for (; tile < n_tiles; tile += (int64_t)nb * n_waves) {
     const int64_t i = tile * 16 + j;
     const bool ok = i < p.B;
@@ -191,50 +268,73 @@ __device__ __forceinline__ void forward16r_body(const FwdArgs &p, float *lds, co
 #pragma unroll
     for (int b = 0; b < 4; ++b) x[b] = xn[b];
     if (tile + (int64_t)nb * n_waves < n_tiles) load_x(tile + (int64_t)nb * n_waves, xn);      // (a wave with a second tile: its rows under this tile)
-    f32x4 h[4];
-    trunk16r_apply<RELU, LN>(tw, x, h, D, ok, fnorm, q);
-    // ---- head ----
-    if constexpr (MODE == 2) {
-      if (ok) {
+    tile16r_step<RELU, LN, MODE>(p, tw, hd, x, p.out, p.actions, p.logp, p.counter, p.counter_dev, tZ, i, ok, j, q);
+  }
+}
+
+// Row sources of one network over an episode: step 0 reads x0 (element (n, m, d) at x0[n x0_sn + m x0_sm + d]), step t >= 1 the
+// env output of step t - 1 at xp[(t - 1) xp_st + n xp_sn + m xp_sm + d]; row i = (n, m) = (i / M, i % M)
+struct EpisodeSrc {
+  const float *x0;
+  int64_t x0_sn, x0_sm;
+  const float *xp;
+  int64_t xp_st, xp_sn, xp_sm;
+};
+
+// One network over a whole episode (mappo_rollout_episode): steps t = 0 .. n_steps - 1 of this wave's tiles in one loop.  The
+// weights are loaded once; the rows of the next (step, tile) are requested before the math of the current one.  Outputs of
+// step t: MODE 1 -> actions / logp + t B with counter p.counter + (*p.counter_dev) + t; MODE 0 -> p.out + t B, the last step
+// (t == n_last) -> last_out.  Every tile goes through tile16r_step: the stepwise kernel's arithmetic, row for row.
+template <bool RELU, int LN, int MODE>
+__device__ __forceinline__ void episode16r_body(const FwdArgs &p, const EpisodeSrc &s, const int M, const int n_steps, const int n_last,
+                                                float *last_out, float *lds, const int bid, const int nb) {
+  const int n_waves = blockDim.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), j = lane & 15, q = lane >> 4;
+  const int D = p.desc.in_dim, A = p.desc.out_dim;
+  const int64_t n_tiles = (p.B + 15) / 16;
+  float *tZ = lds + wave * 16 * TP;
+  const int64_t tile0 = (int64_t)bid * n_waves + wave, tstride = (int64_t)nb * n_waves;
+  if (tile0 >= n_tiles) return;
+  const int n_my = (int)((n_tiles - tile0 + tstride - 1) / tstride);          // tiles of this wave, visited at every step
+  const int n_items = n_steps * n_my;
+  auto load_x = [&](int it, f32x4 (&xv)[4]) {
+    const int t = it / n_my, k = it - t * n_my;
+    const int64_t i = (tile0 + k * tstride) * 16 + j;
+    const int64_t row = i < p.B ? i : 0;
+    const float *base = t == 0 ? s.x0 : s.xp + (int64_t)(t - 1) * s.xp_st;
+    const int64_t sn = t == 0 ? s.x0_sn : s.xp_sn, sm = t == 0 ? s.x0_sm : s.xp_sm;
+    const int64_t off = (row / M) * sn + (row % M) * sm;
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < 4; ++b)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) p.out[(int64_t)(16 * b + 4 * q + r) * p.B + i] = h[b][r];
-      }
-    } else {
-      f32x4 z[NBH > 0 ? NBH : 1];
+      for (int r = 0; r < 4; ++r) xv[b][r] = base[off + min(16 * b + 4 * q + r, D - 1)];
+  };
+  // rows of the first step before the weights (the order of forward16r_body)
+  f32x4 xn[4];
+  load_x(0, xn);
+  Trunk16R<LN> tw;
+  trunk16r_load<LN>(tw, p.params, p.off, p.desc, j, q);
+  Head16R<MODE> hd;
+  head16r_load<MODE>(hd, p.params, p.off, A, j, q);
+  const uint64_t ctr0 = p.counter + (MODE == 1 && p.counter_dev ? *p.counter_dev : 0ull);      // read once: the word is fixed for the launch
+  // Everything above is in flight; the first step needs (nearly) all of it.  Without this wait the loop's first use of a weight
+  // register is a wait on a load from before the loop, which the counter cannot tell apart from the row prefetch issued inside
+  // it: every step would then wait for the NEXT step's rows (vmcnt(0)) — one memory round trip per step.
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_sched_barrier(0);
+  for (int it = 0; it < n_items; ++it) {
+    const int t = it / n_my, k = it - t * n_my;
+    const int64_t i = (tile0 + k * tstride) * 16 + j;
+    const bool ok = i < p.B;
+    f32x4 x[4];
 #pragma unroll
-      for (int bo = 0; bo < NBH; ++bo) {
-        z[bo] = bhv[bo];
-        if (bo == 0 || A > 16) {
-#pragma unroll
-          for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) z[bo] = mfma16(wh[bo][b][r], h[b][r], z[bo]);
-        }
-      }
-      if constexpr (MODE == 0) {
-        if (A == 1) { if (ok && q == 0) p.out[i] = z[0][0]; }
-        else if (ok) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { const int a = 4 * q + r; if (a < A) p.out[i * A + a] = z[0][r]; }     // (out_dim <= 16 through this path)
-        }
-      } else {
-#pragma unroll
-        for (int bo = 0; bo < NBH; ++bo)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { const int a = 16 * bo + 4 * q + r; if (a < A) tZ[j * TP + a] = z[bo][r]; }
-        wave_lds_sync();
-        if (ok && q == 0) {
-          const uint64_t ctr = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);
-          float action, logp;
-          categorical_act_lane(tZ + j * TP, A, p.avail ? p.avail + i * A : nullptr, p.deterministic != 0, p.seed, ctr, (uint64_t)i, action, logp);
-          p.actions[i] = action;
-          p.logp[i] = logp;
-        }
-        wave_lds_sync();
-      }
-    }
+    for (int b = 0; b < 4; ++b) x[b] = xn[b];
+    if (it + 1 < n_items) load_x(it + 1, xn);                                    // the next step's rows under this step's math
+    const int64_t so = (int64_t)t * p.B;
+    float *out = MODE == 0 ? (t == n_last ? last_out : p.out + so) : nullptr;
+    tile16r_step<RELU, LN, MODE, true>(p, tw, hd, x, out, MODE == 1 ? p.actions + so : nullptr, MODE == 1 ? p.logp + so : nullptr,
+                                       ctr0 + (uint64_t)t, nullptr, tZ, i, ok, j, q);
   }
 }
 

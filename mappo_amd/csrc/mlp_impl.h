@@ -727,6 +727,28 @@ __global__ __launch_bounds__(256, 1) void rollout_step_kernel(StepArgs s) {
   else insert_mpe_body(s.ins, bid - s.nA - s.nC, s.nI);
 }
 
+// One rollout episode in one launch (mappo_rollout_episode): for an env whose output for the whole episode exists before the
+// episode starts (and does not depend on the actions), workgroups [0, nA) run the actor's get_actions of steps 0 .. T - 1,
+// [nA, nA + nC) the critic's get_values of steps 0 .. T (step T: the bootstrap values), the rest copy the env output of every
+// step into the buffer slots.  Rows of different threads never interact and the weights do not change, so each wave walks
+// its tiles through the steps on its own: no inter-workgroup synchronisation.
+struct EpisodeArgs {
+  FwdArgs a, c;                  // a.actions / a.logp, c.out: [T][B]
+  EpisodeSrc sa, sc;
+  float *next_values;            // [B]: the critic at step T
+  InsertArgs ins;                // the insert of step 0's env output; step t: sources + t * *_st, destinations t slots further
+  int64_t ins_obs_st, ins_rew_st, ins_done_st;
+  int T, M, nA, nC, nI;
+};
+template <bool RELU, int LN>
+__global__ __launch_bounds__(256, 1) void rollout_episode_kernel(EpisodeArgs e) {
+  extern __shared__ __align__(16) float lds[];
+  const int bid = blockIdx.x;
+  if (bid < e.nA) episode16r_body<RELU, LN, 1>(e.a, e.sa, e.M, e.T, -1, nullptr, lds, bid, e.nA);
+  else if (bid < e.nA + e.nC) episode16r_body<RELU, LN, 0>(e.c, e.sc, e.M, e.T + 1, e.T, e.next_values, lds, bid - e.nA, e.nC);
+  else insert_mpe_episode_body<8>(e.ins, e.ins_obs_st, e.ins_rew_st, e.ins_done_st, e.T, bid - e.nA - e.nC, e.nI);
+}
+
 // trunk features of a recurrent network (mappo_mlp_features, in_dim <= 64) on the same register-resident 16x16x4 path
 template <bool RELU, int LN>
 __global__ __launch_bounds__(256, 1) void features16_kernel(FwdArgs a) {
@@ -2030,6 +2052,81 @@ extern "C" int mappo_rollout_step(const float *actor_params, const mappo_net_des
   }
   if (rc) return rc;
   MAPPO_CHECK_LAUNCH("rollout_step");
+  return MAPPO_OK;
+}
+
+// ---- one rollout episode in one launch (rollout_episode_kernel) ---------------------------------------------------------------
+#define EPISODE_WAVES 1                                    // waves per workgroup (measured: DESIGN.md, launch structure)
+template <bool R, int L>
+static int episode_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const EpisodeArgs &a) {
+  hipLaunchKernelGGL((rollout_episode_kernel<R, L>), grid, block, lds_bytes, st, a);
+  return MAPPO_OK;
+}
+
+extern "C" int mappo_rollout_episode(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
+                                     const mappo_net_desc *critic_desc, int32_t T, int32_t N, int32_t M, const float *env_obs,
+                                     int64_t obs_stride_t, int64_t obs_stride_n, int64_t obs_stride_m, const float *rewards,
+                                     int64_t rew_stride_t, int64_t rew_stride_n, int64_t rew_stride_m, const uint8_t *dones,
+                                     int64_t done_stride_t, int64_t done_stride_n, int64_t done_stride_m, int32_t deterministic,
+                                     uint64_t seed, uint64_t counter, const uint64_t *counter_dev, float *obs_buf, float *share_buf,
+                                     float *rew_buf, float *mask_buf, float *actions, float *logp, float *values, float *next_values,
+                                     int32_t centralized, mappo_stream_t stream) {
+  if (int rc = check_desc(actor_desc, "rollout_episode")) return rc;
+  if (int rc = check_desc(critic_desc, "rollout_episode")) return rc;
+  MAPPO_REQUIRE(actor_desc->in_dim <= MAXD && critic_desc->in_dim <= MAXD, "rollout_episode: in_dim %d / %d: both networks must be narrow (<= %d)",
+                actor_desc->in_dim, critic_desc->in_dim, MAXD);
+  MAPPO_REQUIRE(actor_desc->layer_N == critic_desc->layer_N && actor_desc->use_relu == critic_desc->use_relu,
+                "rollout_episode: actor and critic must share layer_N and the activation");
+  MAPPO_REQUIRE(critic_desc->out_dim == 1, "rollout_episode: critic out_dim must be 1");
+  MAPPO_REQUIRE(T >= 1 && N >= 1 && M >= 1, "rollout_episode: bad shape T=%d N=%d M=%d", T, N, M);
+  MAPPO_REQUIRE(obs_stride_t >= 0 && obs_stride_n >= 0 && obs_stride_m >= 0 && rew_stride_t >= 0 && rew_stride_n >= 0 && rew_stride_m >= 0 &&
+                done_stride_t >= 0 && done_stride_n >= 0 && done_stride_m >= 0, "rollout_episode: negative stride");
+  const int D = actor_desc->in_dim;
+  if (centralized)      // share row of (n, m) = the thread's agents side by side, read in place: the agents must be contiguous
+    MAPPO_REQUIRE(critic_desc->in_dim == M * D && obs_stride_m == D, "rollout_episode: centralized critic needs in_dim M*D = %d (got %d) and "
+                  "agent rows D apart in the env output (stride %lld)", M * D, critic_desc->in_dim, (long long)obs_stride_m);
+  else
+    MAPPO_REQUIRE(critic_desc->in_dim == D, "rollout_episode: critic in_dim %d != actor in_dim %d", critic_desc->in_dim, D);
+  MAPPO_REQUIRE(actor_params && critic_params && env_obs && rewards && dones && obs_buf && share_buf && rew_buf && mask_buf && actions && logp &&
+                values && next_values, "rollout_episode: bad arguments (null pointer)");
+  MAPPO_CLEAR_STICKY();
+  const int64_t B = (int64_t)N * M, S = critic_desc->in_dim;
+  const int64_t n_tiles = (B + 15) / 16;
+  // waves per workgroup (MAPPO_EPISODE_WAVES = 1 / 2 / 4: A/B of the geometry)
+  int nw = EPISODE_WAVES;
+  if (const char *ev = getenv("MAPPO_EPISODE_WAVES")) { const int v = atoi(ev); if (v == 1 || v == 2 || v == 4) nw = v; }
+  int64_t nb = (n_tiles + nw - 1) / nw;
+  if (nb > 2 * NUM_CU / nw) nb = 2 * NUM_CU / nw;         // at most 512 waves per network: beyond that a wave walks several tiles per step
+  EpisodeArgs e = {};
+  e.a.params = actor_params; e.a.actions = actions; e.a.logp = logp; e.a.desc = *actor_desc; e.a.B = B; e.a.deterministic = deterministic;
+  e.a.seed = seed; e.a.counter = counter; e.a.counter_dev = counter_dev; e.a.off = net_offsets(e.a.desc);
+  e.c.params = critic_params; e.c.out = values; e.c.desc = *critic_desc; e.c.B = B; e.c.off = net_offsets(e.c.desc);
+  e.sa = EpisodeSrc{obs_buf, (int64_t)M * D, D, env_obs, obs_stride_t, obs_stride_n, obs_stride_m};
+  e.sc = EpisodeSrc{share_buf, (int64_t)M * S, S, env_obs, obs_stride_t, obs_stride_n, centralized ? 0 : obs_stride_m};
+  e.next_values = next_values;
+  InsertArgs &i = e.ins;
+  i.obs = env_obs; i.obs_sn = obs_stride_n; i.obs_sm = obs_stride_m; i.rew = rewards; i.rew_sn = rew_stride_n; i.rew_sm = rew_stride_m;
+  i.done = dones; i.done_sn = done_stride_n; i.done_sm = done_stride_m;
+  i.obs_dst = obs_buf + B * D; i.share_dst = share_buf + B * S; i.rew_dst = rew_buf; i.mask_dst = mask_buf + B;    // slots 1, 1, 0, 1
+  i.N = N; i.M = M; i.D = D; i.centralized = centralized;
+  e.ins_obs_st = obs_stride_t; e.ins_rew_st = rew_stride_t; e.ins_done_st = done_stride_t;
+  e.T = T; e.M = M; e.nA = (int)nb; e.nC = (int)nb;
+  // insert: the SIMDs the network waves leave (one wave per SIMD at this kernel's register count), 8 elements per lane per pass
+  int64_t n_ins_waves = ((int64_t)T * B * S + 64 * 8 * 2 - 1) / (64 * 8 * 2);
+  const int64_t free_waves = 4 * NUM_CU - 2 * nb * nw;
+  if (n_ins_waves > free_waves) n_ins_waves = free_waves < 64 ? 64 : free_waves;
+  e.nI = (int)((n_ins_waves + nw - 1) / nw);
+  const dim3 grid((unsigned)(e.nA + e.nC + e.nI)), block(WAVE * nw);
+  const size_t lds_bytes = sizeof(float) * 16 * TP * nw;   // the actor's [16][TP] logits tile per wave
+  const bool relu = actor_desc->use_relu != 0;
+  int rc;
+  switch (actor_desc->layer_N) {
+    case 0: rc = relu ? episode_launch<true, 0>(grid, block, lds_bytes, as_stream(stream), e) : episode_launch<false, 0>(grid, block, lds_bytes, as_stream(stream), e); break;
+    case 1: rc = relu ? episode_launch<true, 1>(grid, block, lds_bytes, as_stream(stream), e) : episode_launch<false, 1>(grid, block, lds_bytes, as_stream(stream), e); break;
+    default: rc = relu ? episode_launch<true, 2>(grid, block, lds_bytes, as_stream(stream), e) : episode_launch<false, 2>(grid, block, lds_bytes, as_stream(stream), e); break;
+  }
+  if (rc) return rc;
+  MAPPO_CHECK_LAUNCH("rollout_episode");
   return MAPPO_OK;
 }
 #endif

@@ -44,6 +44,22 @@ class SyntheticMPEEnv:
         dones = self._done_true if (self.t % self.T == 0) else self._done_false   # fixed per step index of an episode
         return obs, rewards, dones, None
 
+    def episode_block(self):
+        """The env output of a whole episode at once (the runner's one-launch episode, mappo_rollout_episode): the pool step()
+        would hand out step by step, drawn by the same call, and `t` advanced by T.  Returns (obs [T, N, M, D], rewards
+        [T, N, M, 1], dones [T, N, M] bool — true on the last step only, as step() reports it); views, valid until the next
+        episode.  Needs an episode-aligned `t`."""
+        assert self.t % self.T == 0, "episode_block: t must be at an episode boundary"
+        T, N, M, D = self.T, self.N, self.M, self.D
+        self._pool = torch.randn(T, N, M * D + 1, device=self.device)
+        self.t += T
+        obs = self._pool[:, :, :M * D].view(T, N, M, D)
+        rewards = self._pool[:, :, M * D:].view(T, N, 1, 1).expand(T, N, M, 1)
+        if getattr(self, "_dones_episode", None) is None:
+            self._dones_episode = torch.zeros(T, N, M, dtype=torch.bool, device=self.device)
+            self._dones_episode[T - 1] = True
+        return obs, rewards, self._dones_episode
+
     def close(self):
         pass
 

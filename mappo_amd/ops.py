@@ -252,6 +252,40 @@ def rollout_step(actor_params, actor_desc, critic_params, critic_desc, obs, shar
     _lib.check(rc, "mappo_rollout_step")
 
 
+def _strided(t, dtype):
+    """Pointer of a (possibly strided) device view, for the entry points that take explicit strides."""
+    if not t.is_cuda:
+        raise _lib.MappoHipError("mappo_amd ops need tensors in HBM (cuda/hip device); got a CPU tensor — there is no CPU fallback")
+    if t.dtype != dtype:
+        raise TypeError(f"expected {dtype}, got {t.dtype}")
+    return C.c_void_p(t.data_ptr())
+
+
+def rollout_episode(actor_params, actor_desc, critic_params, critic_desc, obs, rewards, dones, deterministic, seed, counter, counter_dev,
+                    obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values, next_values, centralized):
+    """A whole rollout episode in one launch (mappo_rollout_episode).  obs [T, N, M, D], rewards [T, N, M] (or [T, N, M, 1]),
+    dones [T, N, M] bool: the env output of every step, any strides (d contiguous); the buffer arrays are the contiguous
+    SharedReplayBuffer tensors (obs / share_obs / masks [T+1, ...], rewards / actions / action_log_probs [T, ...], value_preds
+    [T+1, ...] of which slots 0..T-1 are written); next_values [N*M] receives the critic of step T."""
+    T, N, M, D = obs.shape
+    if obs.stride(3) != 1:
+        raise ValueError("rollout_episode: obs rows must be contiguous in the feature dimension")
+    if rewards.dim() == 4:
+        rewards = rewards[..., 0]
+    if tuple(rewards.shape) != (T, N, M) or tuple(dones.shape) != (T, N, M):
+        raise ValueError(f"rollout_episode: rewards {tuple(rewards.shape)} / dones {tuple(dones.shape)} do not match obs {tuple(obs.shape)}")
+    R = N * M
+    rc = _lib.load().mappo_rollout_episode(_ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), int(T), int(N),
+                                           int(M), _strided(obs, torch.float32), int(obs.stride(0)), int(obs.stride(1)), int(obs.stride(2)),
+                                           _strided(rewards, torch.float32), int(rewards.stride(0)), int(rewards.stride(1)), int(rewards.stride(2)),
+                                           _strided(dones, torch.bool), int(dones.stride(0)), int(dones.stride(1)), int(dones.stride(2)),
+                                           int(bool(deterministic)), int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
+                                           _ptr(counter_dev, torch.int64, allow_none=True), _ptr(obs_buf), _ptr(share_buf), _ptr(rew_buf),
+                                           _ptr(mask_buf), _ptr(actions), _ptr(logp), _ptr(values), _ptr(next_values),
+                                           int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode")
+
+
 def mlp_backward_slabs(B):
     return int(_lib.load().mappo_mlp_backward_slabs(int(B)))
 

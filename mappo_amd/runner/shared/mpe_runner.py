@@ -19,6 +19,7 @@ class MPERunner(Runner):
         self._onehot = None
         self._rollout_graph = None          # None -> "warm" -> CUDAGraph
         self._fuse_step = bool(getattr(self.all_args, "fuse_rollout_step", True))
+        self._fuse_episode = bool(getattr(self.all_args, "fuse_rollout_episode", True))
         self._next_values = None
         # the rollout has no collective in it, so data-parallel ranks capture it too
         self._use_graph = bool(getattr(self.all_args, "use_hip_graph", True)) and bool(getattr(self.envs, "graph_safe", False))
@@ -67,6 +68,17 @@ class MPERunner(Runner):
         infos = None
         self.trainer.policy.actor._counter_dev.add_(self.episode_length)   # fresh sampling stream per (replayed) episode
         fuse = self._fuse_step and self.trainer.policy.can_fuse_step()
+        if fuse and self._fuse_episode and self._episode_env() and self.trainer.policy.can_fuse_episode():
+            # the env's output for the whole episode exists up front and ignores the actions: the episode is ONE launch
+            # (mappo_rollout_episode), same buffer contents as the stepwise loop below; GAE stays its own launch
+            b = self.buffer
+            if self._next_values is None:
+                self._next_values = torch.empty(b.n_rollout_threads * b.num_agents, device=b.device)
+            nv = self.trainer.policy.collect_episode_fused(b, self.envs.episode_block(), self._next_values, self.use_centralized_V)
+            b.step = 0
+            self.trainer.prep_rollout()
+            b.compute_returns(nv, self.trainer.value_normalizer)
+            return infos
         pending = None                     # env output of the previous step, not yet in the buffer (fused path)
         for step in range(self.episode_length):
             if fuse:
@@ -109,6 +121,18 @@ class MPERunner(Runner):
             return infos
         self.compute()
         return infos
+
+    def _episode_env(self):
+        """The env hands out the next whole episode (SyntheticMPEEnv.episode_block) on the device the policy's kernels read —
+        the same device test collect_step_fused applies to the env output, so a run the stepwise fused path declines keeps
+        the stepwise loop."""
+        env = self.envs
+        if not hasattr(env, "episode_block") or env.t % self.episode_length != 0 or self._staging is not None:
+            return False
+        dev = torch.device(env.device)
+        if dev.type == "cuda" and dev.index is None:            # where its tensors land
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return dev == self.trainer.policy.device
 
     def rollout(self):
         """T x (collect, env.step, insert) + compute().  With a vec-env that declares `graph_safe` (device-resident,
