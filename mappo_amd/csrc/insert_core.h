@@ -32,13 +32,15 @@ __device__ __forceinline__ void insert_mpe_body(const InsertArgs &p, int bid, in
 // The MPE insert of a whole episode (rollout_episode_kernel): p describes step 0 (sources: the env output of step 0, destinations:
 // the buffer slots it goes to); step t reads the sources t * *_st further and writes t slots further.  Flattened over (step,
 // element), U elements per lane per pass with every load of a pass issued before its stores: one dependent round trip per
-// element (insert_mpe_body's loop) made this role the long pole of the launch.
-template <int U>
-__device__ __forceinline__ void insert_mpe_episode_body(const InsertArgs &p, int64_t obs_st, int64_t rew_st, int64_t done_st, int T,
-                                                        int bid, int nb) {
+// element (insert_mpe_body's loop) made this role the long pole of the launch.  Wave w of the nw waves that share the copy.
+// I: the type of the (step, row, element) split of an element index — three divisions per element, which in 64 bits are
+// software sequences that made the copy instruction-bound; 32 bits whenever the episode's element count fits.
+template <int U, typename I>
+__device__ __forceinline__ void insert_mpe_episode_run(const InsertArgs &p, int64_t obs_st, int64_t rew_st, int64_t done_st, int T,
+                                                       int w, int nw) {
   const int S = p.centralized ? p.M * p.D : p.D;
-  const int64_t R = (int64_t)p.N * p.M, RS = R * S, total = (int64_t)T * RS, nthr = (int64_t)nb * blockDim.x;
-  for (int64_t e0 = (int64_t)bid * blockDim.x + threadIdx.x; e0 < total; e0 += U * nthr) {
+  const int64_t R = (int64_t)p.N * p.M, RS = R * S, total = (int64_t)T * RS, nthr = (int64_t)nw * WAVE;
+  for (int64_t e0 = (int64_t)w * WAVE + (threadIdx.x & (WAVE - 1)); e0 < total; e0 += U * nthr) {
     float v[U], rw[U];
     uint8_t dn[U];                                   // raw: a compare here would wait for the load (and every load before it)
     int64_t tn[U];                                   // t * R + nm: the row's index in the [T][R] slots
@@ -48,17 +50,17 @@ __device__ __forceinline__ void insert_mpe_episode_body(const InsertArgs &p, int
       const int64_t e = e0 + u * nthr;
       jj[u] = -1;
       if (e < total) {
-        const int64_t t = e / RS, rem = e - t * RS, nm = rem / S;
-        const int j = (int)(rem - nm * S);
-        const int n = (int)(nm / p.M), m = (int)(nm - (int64_t)n * p.M);
+        const I t = (I)e / (I)RS, rem = (I)e - t * (I)RS, nm = rem / (I)S;
+        const int j = (int)(rem - nm * (I)S);
+        const int n = (int)(nm / (I)p.M), m = (int)(nm - (I)n * (I)p.M);
         const int ms = p.centralized ? j / p.D : m, d = p.centralized ? j - ms * p.D : j;      // source agent / feature
-        v[u] = p.obs[t * obs_st + n * p.obs_sn + ms * p.obs_sm + d];
-        tn[u] = t * R + nm;
+        v[u] = p.obs[(int64_t)t * obs_st + n * p.obs_sn + ms * p.obs_sm + d];
+        tn[u] = (int64_t)t * R + (int64_t)nm;
         dd[u] = (!p.centralized || ms == m) ? d : -1;                                        // each obs element exactly once
         jj[u] = j;
         if (j == 0) {
-          rw[u] = p.rew[t * rew_st + n * p.rew_sn + m * p.rew_sm];
-          dn[u] = p.done[t * done_st + n * p.done_sn + m * p.done_sm];
+          rw[u] = p.rew[(int64_t)t * rew_st + n * p.rew_sn + m * p.rew_sm];
+          dn[u] = p.done[(int64_t)t * done_st + n * p.done_sn + m * p.done_sm];
         }
       }
     }
@@ -78,6 +80,13 @@ __device__ __forceinline__ void insert_mpe_episode_body(const InsertArgs &p, int
       }
     }
   }
+}
+template <int U>
+__device__ __forceinline__ void insert_mpe_episode_body(const InsertArgs &p, int64_t obs_st, int64_t rew_st, int64_t done_st, int T,
+                                                        int w, int nw) {
+  const int64_t total = (int64_t)T * p.N * p.M * (p.centralized ? p.M * p.D : p.D);
+  if (total <= (int64_t)UINT32_MAX) insert_mpe_episode_run<U, uint32_t>(p, obs_st, rew_st, done_st, T, w, nw);
+  else insert_mpe_episode_run<U, int64_t>(p, obs_st, rew_st, done_st, T, w, nw);
 }
 
 // ---- the SMAC rollout insert (insert.hip: mappo_insert_smac) as a device function, shared with the fused recurrent rollout step ----

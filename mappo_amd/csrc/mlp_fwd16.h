@@ -281,25 +281,24 @@ struct EpisodeSrc {
   int64_t xp_st, xp_sn, xp_sm;
 };
 
-// One network over a whole episode (mappo_rollout_episode): steps t = 0 .. n_steps - 1 of this wave's tiles in one loop.  The
-// weights are loaded once; the rows of the next (step, tile) are requested before the math of the current one.  Outputs of
-// step t: MODE 1 -> actions / logp + t B with counter p.counter + (*p.counter_dev) + t; MODE 0 -> p.out + t B, the last step
-// (t == n_last) -> last_out.  Every tile goes through tile16r_step: the stepwise kernel's arithmetic, row for row.
+// One network over a whole episode (mappo_rollout_episode): the (step, tile) items t * n_tiles + tile, t = 0 .. n_steps - 1,
+// dealt to the network's nw waves: wave w takes items w, w + nw, w + 2 nw, ...  Nothing in the episode orders the items in time
+// (the env output exists up front, the networks carry no state, sampling of step t uses counter ctr0 + t and row i), so the
+// waves of a network split the steps between them instead of each walking one tile through all of them.  The weights are loaded
+// once per wave; the rows of the next item are requested before the math of the current one.  Outputs of step t: MODE 1 ->
+// actions / logp + t B with counter p.counter + (*p.counter_dev) + t; MODE 0 -> p.out + t B, the last step (t == n_last) ->
+// last_out.  Every item goes through tile16r_step: the stepwise kernel's arithmetic, row for row.  tZ: this wave's [16][TP]
+// logits tile (MODE 1).
 template <bool RELU, int LN, int MODE>
 __device__ __forceinline__ void episode16r_body(const FwdArgs &p, const EpisodeSrc &s, const int M, const int n_steps, const int n_last,
-                                                float *last_out, float *lds, const int bid, const int nb) {
-  const int n_waves = blockDim.x / WAVE;
-  const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), j = lane & 15, q = lane >> 4;
+                                                float *last_out, float *tZ, const int w, const int nw) {
+  const int lane = threadIdx.x & (WAVE - 1), j = lane & 15, q = lane >> 4;
   const int D = p.desc.in_dim, A = p.desc.out_dim;
-  const int64_t n_tiles = (p.B + 15) / 16;
-  float *tZ = lds + wave * 16 * TP;
-  const int64_t tile0 = (int64_t)bid * n_waves + wave, tstride = (int64_t)nb * n_waves;
-  if (tile0 >= n_tiles) return;
-  const int n_my = (int)((n_tiles - tile0 + tstride - 1) / tstride);          // tiles of this wave, visited at every step
-  const int n_items = n_steps * n_my;
-  auto load_x = [&](int it, f32x4 (&xv)[4]) {
-    const int t = it / n_my, k = it - t * n_my;
-    const int64_t i = (tile0 + k * tstride) * 16 + j;
+  const int64_t n_tiles = (p.B + 15) / 16, n_items = (int64_t)n_steps * n_tiles;
+  if (w >= n_items) return;
+  auto load_x = [&](int64_t it, f32x4 (&xv)[4]) {
+    const int t = (int)(it / n_tiles);
+    const int64_t i = (it - t * n_tiles) * 16 + j;
     const int64_t row = i < p.B ? i : 0;
     const float *base = t == 0 ? s.x0 : s.xp + (int64_t)(t - 1) * s.xp_st;
     const int64_t sn = t == 0 ? s.x0_sn : s.xp_sn, sm = t == 0 ? s.x0_sm : s.xp_sm;
@@ -309,28 +308,28 @@ __device__ __forceinline__ void episode16r_body(const FwdArgs &p, const EpisodeS
 #pragma unroll
       for (int r = 0; r < 4; ++r) xv[b][r] = base[off + min(16 * b + 4 * q + r, D - 1)];
   };
-  // rows of the first step before the weights (the order of forward16r_body)
+  // rows of the first item before the weights (the order of forward16r_body)
   f32x4 xn[4];
-  load_x(0, xn);
+  load_x(w, xn);
   Trunk16R<LN> tw;
   trunk16r_load<LN>(tw, p.params, p.off, p.desc, j, q);
   Head16R<MODE> hd;
   head16r_load<MODE>(hd, p.params, p.off, A, j, q);
   const uint64_t ctr0 = p.counter + (MODE == 1 && p.counter_dev ? *p.counter_dev : 0ull);      // read once: the word is fixed for the launch
-  // Everything above is in flight; the first step needs (nearly) all of it.  Without this wait the loop's first use of a weight
+  // Everything above is in flight; the first item needs (nearly) all of it.  Without this wait the loop's first use of a weight
   // register is a wait on a load from before the loop, which the counter cannot tell apart from the row prefetch issued inside
-  // it: every step would then wait for the NEXT step's rows (vmcnt(0)) — one memory round trip per step.
+  // it: every item would then wait for the NEXT item's rows (vmcnt(0)) — one memory round trip per item.
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_sched_barrier(0);
-  for (int it = 0; it < n_items; ++it) {
-    const int t = it / n_my, k = it - t * n_my;
-    const int64_t i = (tile0 + k * tstride) * 16 + j;
+  for (int64_t it = w; it < n_items; it += nw) {
+    const int t = (int)(it / n_tiles);
+    const int64_t i = (it - t * n_tiles) * 16 + j;
     const bool ok = i < p.B;
     f32x4 x[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) x[b] = xn[b];
-    if (it + 1 < n_items) load_x(it + 1, xn);                                    // the next step's rows under this step's math
+    if (it + nw < n_items) load_x(it + nw, xn);                                  // the next item's rows under this item's math
     const int64_t so = (int64_t)t * p.B;
     float *out = MODE == 0 ? (t == n_last ? last_out : p.out + so) : nullptr;
     tile16r_step<RELU, LN, MODE, true>(p, tw, hd, x, out, MODE == 1 ? p.actions + so : nullptr, MODE == 1 ? p.logp + so : nullptr,

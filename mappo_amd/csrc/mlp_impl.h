@@ -728,25 +728,28 @@ __global__ __launch_bounds__(256, 1) void rollout_step_kernel(StepArgs s) {
 }
 
 // One rollout episode in one launch (mappo_rollout_episode): for an env whose output for the whole episode exists before the
-// episode starts (and does not depend on the actions), workgroups [0, nA) run the actor's get_actions of steps 0 .. T - 1,
-// [nA, nA + nC) the critic's get_values of steps 0 .. T (step T: the bootstrap values), the rest copy the env output of every
-// step into the buffer slots.  Rows of different threads never interact and the weights do not change, so each wave walks
-// its tiles through the steps on its own: no inter-workgroup synchronisation.
+// episode starts (and does not depend on the actions), waves [0, wA) run the actor's get_actions of steps 0 .. T - 1, waves
+// [wA, wA + wC) the critic's get_values of steps 0 .. T (step T: the bootstrap values), each network's (step, tile) items dealt
+// over its waves; waves [wI0, wAll) then copy the env output of every step into the buffer slots (wI0 = 0: every wave, after its
+// items; wI0 = wA + wC: waves of their own).  Rows of different threads never interact and the weights do not change: no
+// inter-workgroup synchronisation.
 struct EpisodeArgs {
   FwdArgs a, c;                  // a.actions / a.logp, c.out: [T][B]
   EpisodeSrc sa, sc;
   float *next_values;            // [B]: the critic at step T
   InsertArgs ins;                // the insert of step 0's env output; step t: sources + t * *_st, destinations t slots further
   int64_t ins_obs_st, ins_rew_st, ins_done_st;
-  int T, M, nA, nC, nI;
+  int T, M, wA, wC, wI0, wAll;
 };
 template <bool RELU, int LN>
 __global__ __launch_bounds__(256, 1) void rollout_episode_kernel(EpisodeArgs e) {
   extern __shared__ __align__(16) float lds[];
-  const int bid = blockIdx.x;
-  if (bid < e.nA) episode16r_body<RELU, LN, 1>(e.a, e.sa, e.M, e.T, -1, nullptr, lds, bid, e.nA);
-  else if (bid < e.nA + e.nC) episode16r_body<RELU, LN, 0>(e.c, e.sc, e.M, e.T + 1, e.T, e.next_values, lds, bid - e.nA, e.nC);
-  else insert_mpe_episode_body<8>(e.ins, e.ins_obs_st, e.ins_rew_st, e.ins_done_st, e.T, bid - e.nA - e.nC, e.nI);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const int gw = (int)blockIdx.x * (int)(blockDim.x / WAVE) + wave;
+  float *tZ = lds + wave * 16 * TP;
+  if (gw < e.wA) episode16r_body<RELU, LN, 1>(e.a, e.sa, e.M, e.T, -1, nullptr, tZ, gw, e.wA);
+  else if (gw < e.wA + e.wC) episode16r_body<RELU, LN, 0>(e.c, e.sc, e.M, e.T + 1, e.T, e.next_values, tZ, gw - e.wA, e.wC);
+  if (gw >= e.wI0 && gw < e.wAll) insert_mpe_episode_body<16>(e.ins, e.ins_obs_st, e.ins_rew_st, e.ins_done_st, e.T, gw - e.wI0, e.wAll - e.wI0);
 }
 
 // trunk features of a recurrent network (mappo_mlp_features, in_dim <= 64) on the same register-resident 16x16x4 path
@@ -2056,7 +2059,20 @@ extern "C" int mappo_rollout_step(const float *actor_params, const mappo_net_des
 }
 
 // ---- one rollout episode in one launch (rollout_episode_kernel) ---------------------------------------------------------------
-#define EPISODE_WAVES 1                                    // waves per workgroup (measured: DESIGN.md, launch structure)
+// Geometry (measured: DESIGN.md, launch structure).  The kernel holds its weights in registers: one wave per SIMD, so the waves
+// of one launch are at most 4 x NUM_CU and the network items are dealt over all of them; the insert follows every wave's items.
+// Diagnostic overrides for A/B on one build: MAPPO_EPISODE_WAVES (waves per workgroup: 1 / 2 / 4), MAPPO_EPISODE_NET_WAVES
+// (network waves), MAPPO_EPISODE_INS_WAVES (> 0: that many waves of their own for the insert), MAPPO_EPISODE_COST_A (an actor
+// item's cost against a critic item's EPISODE_COST_C, which splits the network waves).
+#define EPISODE_WAVES 1
+#define EPISODE_COST_A 150                                 // per-item costs: the actor samples after its head (measured: DESIGN.md)
+#define EPISODE_COST_C 134
+static int env_int(const char *name, int dflt, int lo, int hi) {
+  const char *ev = getenv(name);
+  if (!ev) return dflt;
+  const int v = atoi(ev);
+  return v < lo ? lo : (v > hi ? hi : v);
+}
 template <bool R, int L>
 static int episode_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const EpisodeArgs &a) {
   hipLaunchKernelGGL((rollout_episode_kernel<R, L>), grid, block, lds_bytes, st, a);
@@ -2092,11 +2108,21 @@ extern "C" int mappo_rollout_episode(const float *actor_params, const mappo_net_
   MAPPO_CLEAR_STICKY();
   const int64_t B = (int64_t)N * M, S = critic_desc->in_dim;
   const int64_t n_tiles = (B + 15) / 16;
-  // waves per workgroup (MAPPO_EPISODE_WAVES = 1 / 2 / 4: A/B of the geometry)
-  int nw = EPISODE_WAVES;
-  if (const char *ev = getenv("MAPPO_EPISODE_WAVES")) { const int v = atoi(ev); if (v == 1 || v == 2 || v == 4) nw = v; }
-  int64_t nb = (n_tiles + nw - 1) / nw;
-  if (nb > 2 * NUM_CU / nw) nb = 2 * NUM_CU / nw;         // at most 512 waves per network: beyond that a wave walks several tiles per step
+  int nw = env_int("MAPPO_EPISODE_WAVES", EPISODE_WAVES, 1, 4);
+  if (nw != 1 && nw != 2) nw = 4;
+  const int n_ins = env_int("MAPPO_EPISODE_INS_WAVES", 0, 0, 4 * NUM_CU - 2);
+  const int n_net = env_int("MAPPO_EPISODE_NET_WAVES", 4 * NUM_CU - n_ins, 2, 4 * NUM_CU);
+  const int64_t cost_a = env_int("MAPPO_EPISODE_COST_A", EPISODE_COST_A, 1, 1000), cost_c = EPISODE_COST_C;
+  // the split of the network waves with the shortest longest wave (items per wave x item cost); no network gets more waves than items
+  const int64_t items_a = (int64_t)T * n_tiles, items_c = (int64_t)(T + 1) * n_tiles;
+  int64_t wa = 1, best = -1;
+  for (int64_t a = 1; a < n_net; ++a) {
+    const int64_t la = (items_a + a - 1) / a * cost_a, lc = (items_c + (n_net - a) - 1) / (n_net - a) * cost_c;
+    const int64_t l = la > lc ? la : lc;
+    if (best < 0 || l < best) { best = l; wa = a; }
+  }
+  const int64_t wc = n_net - wa > items_c ? items_c : n_net - wa;
+  if (wa > items_a) wa = items_a;
   EpisodeArgs e = {};
   e.a.params = actor_params; e.a.actions = actions; e.a.logp = logp; e.a.desc = *actor_desc; e.a.B = B; e.a.deterministic = deterministic;
   e.a.seed = seed; e.a.counter = counter; e.a.counter_dev = counter_dev; e.a.off = net_offsets(e.a.desc);
@@ -2110,13 +2136,10 @@ extern "C" int mappo_rollout_episode(const float *actor_params, const mappo_net_
   i.obs_dst = obs_buf + B * D; i.share_dst = share_buf + B * S; i.rew_dst = rew_buf; i.mask_dst = mask_buf + B;    // slots 1, 1, 0, 1
   i.N = N; i.M = M; i.D = D; i.centralized = centralized;
   e.ins_obs_st = obs_stride_t; e.ins_rew_st = rew_stride_t; e.ins_done_st = done_stride_t;
-  e.T = T; e.M = M; e.nA = (int)nb; e.nC = (int)nb;
-  // insert: the SIMDs the network waves leave (one wave per SIMD at this kernel's register count), 8 elements per lane per pass
-  int64_t n_ins_waves = ((int64_t)T * B * S + 64 * 8 * 2 - 1) / (64 * 8 * 2);
-  const int64_t free_waves = 4 * NUM_CU - 2 * nb * nw;
-  if (n_ins_waves > free_waves) n_ins_waves = free_waves < 64 ? 64 : free_waves;
-  e.nI = (int)((n_ins_waves + nw - 1) / nw);
-  const dim3 grid((unsigned)(e.nA + e.nC + e.nI)), block(WAVE * nw);
+  e.T = T; e.M = M; e.wA = (int)wa; e.wC = (int)wc;
+  e.wI0 = n_ins > 0 ? e.wA + e.wC : 0;
+  e.wAll = e.wA + e.wC + n_ins;
+  const dim3 grid((unsigned)((e.wAll + nw - 1) / nw)), block(WAVE * nw);
   const size_t lds_bytes = sizeof(float) * 16 * TP * nw;   // the actor's [16][TP] logits tile per wave
   const bool relu = actor_desc->use_relu != 0;
   int rc;
