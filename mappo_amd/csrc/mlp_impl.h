@@ -772,6 +772,7 @@ __global__ __launch_bounds__(256, 1) void features16_dual_kernel(FwdArgs a, FwdA
 #ifdef MLP_STAMPS
 #define N_STAMPS 24
 static unsigned long long *g_stamp_host = nullptr;          // [gridDim.x][N_STAMPS], set by mappo_debug_set_stamps (main TU)
+static unsigned long long *g_stamp_waves_host = nullptr;    // [gridDim.x][8][N_STAMPS], set by mappo_debug_set_stamps_waves
 #define STAMP_DECL unsigned long long st_acc_[N_STAMPS] = {}; unsigned long long st_prev_ = __builtin_readcyclecounter();
 #define STAMP(i)                                                          \
   do {                                                                    \
@@ -786,13 +787,25 @@ static unsigned long long *g_stamp_host = nullptr;          // [gridDim.x][N_STA
     if (p.stamps && threadIdx.x == 0)                                                     \
       for (int i_ = 0; i_ < N_STAMPS; ++i_) p.stamps[blockIdx.x * N_STAMPS + i_] = st_acc_[i_]; \
   } while (0)
+// opt-in (mappo_debug_set_stamps_waves, a buffer of its own): every wave its own row [gridDim.x][blockDim.x / WAVE][N_STAMPS]
+// (update16_body: the slowest wave is the one to read), the last slot holding `tag`
+#define STAMP_FLUSH_WAVES(tag)                                                                                     \
+  do {                                                                                                             \
+    if (p.stamps_waves && (threadIdx.x & (WAVE - 1)) == 0) {                                                       \
+      unsigned long long *row_ = p.stamps_waves + ((size_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE) * N_STAMPS; \
+      for (int i_ = 0; i_ < N_STAMPS - 1; ++i_) row_[i_] = st_acc_[i_];                                         \
+      row_[N_STAMPS - 1] = (tag);                                                                                  \
+    }                                                                                                              \
+  } while (0)
 #ifdef MLP_TU_MAIN
 extern "C" int mappo_debug_set_stamps(unsigned long long *buf) { g_stamp_host = buf; return 0; }
+extern "C" int mappo_debug_set_stamps_waves(unsigned long long *buf) { g_stamp_waves_host = buf; return 0; }
 #endif
 #else
 #define STAMP_DECL
 #define STAMP(i) do { } while (0)
 #define STAMP_FLUSH() do { } while (0)
+#define STAMP_FLUSH_WAVES(tag) do { } while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -822,6 +835,7 @@ struct UpdArgs {
   double *partials;          // [gridDim.x][4]
   mappo_ppo_cfg cfg;
   unsigned long long *stamps;   // diagnostic build (-DMLP_STAMPS) only
+  unsigned long long *stamps_waves;   // the same, one row per wave (update16_body)
 };
 
 // sum over the 32 samples of row `f` (= lane) of a [64][TP] tile
@@ -1623,6 +1637,7 @@ int wide16_launch_l1_bwd(const WideBwd16Args &w, dim3 grid, hipStream_t st) {
 #define LDS_DYN_MAX (LDS_LIMIT - LDS_STATIC) // what hipFuncAttributeMaxDynamicSharedMemorySize may be raised to
 #define NUM_CU 256
 #define UPD16_LDS_MAX (LDS_LIMIT - 256)          // the 16-sample-tile update kernels have no static __shared__
+static_assert(L16<0, 1, false>::LDS_CAP * 4 == UPD16_LDS_MAX, "L16::LDS_CAP is UPD16_LDS_MAX in floats");
 
 // One launch of mlp_update_kernel<RELU, LN, HEAD, *>.  The 72 instantiations of that kernel are spread over the
 // translation units mlp_upd_r{0,1}_l{0,1,2}.hip (one (RELU, LN) pair each, compiled in parallel); mlp.hip holds the
@@ -2388,6 +2403,7 @@ static int launch_update(UpdArgs &a, hipStream_t st, const char *who) {
   }
 #ifdef MLP_STAMPS
   a.stamps = g_stamp_host;
+  a.stamps_waves = g_stamp_waves_host;
 #endif
   int rc;
   const bool trunk16 = HEAD == 3 && upd16_trunk_eligible(d);
@@ -2584,6 +2600,10 @@ extern "C" int mappo_actor_critic_update(const float *actor_params, const mappo_
     if (int rc = prep16(d.a, true, "actor_critic_update")) return rc;
     if (int rc = prep16(d.c, false, "actor_critic_update")) return rc;
     upd16_split(a.desc, c.desc, B, d.nA, d.nC);
+#ifdef MLP_STAMPS
+    a.stamps = c.stamps = g_stamp_host;                          // indexed by blockIdx.x: the actor's rows first
+    a.stamps_waves = c.stamps_waves = g_stamp_waves_host;
+#endif
     // the network with fewer workgroups: its missing slab / partial rows are zero-filled by the other one's workgroups
     if (d.nA < d.nC) { d.c.zero_row0 = d.nA; d.c.zero_row1 = d.nC; d.c.zero_col0 = actor_col0; d.c.zero_cols = a.off.total; d.c.zero_partials = actor_partials; }
     if (d.nC < d.nA) { d.a.zero_row0 = d.nC; d.a.zero_row1 = d.nA; d.a.zero_col0 = critic_col0; d.a.zero_cols = c.off.total; d.a.zero_partials = critic_partials; }

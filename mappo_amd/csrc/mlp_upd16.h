@@ -60,11 +60,17 @@ struct L16 {
   // epilogue (overlaid on the tile area): [1024 scratch | chunk buffer N_WAVES x CH x 256 | flat gradient (<= PMAX)]
   static constexpr int DMAX = XL1 ? 0 : (WIDE ? 64 : 32);
   static constexpr int PMAX = 2 * DMAX + HID * DMAX + 3 * HID + (LN > 0 ? HID * HID + 3 * HID : 0) + (HEAD == 1 ? 16 * HID + 16 : HID + 1);
-  static constexpr int EPI4 = 1024 + N_WAVES * 4 * 256 + PMAX;
-  static constexpr int TILE_AREA = N_WAVES * WAVE_STRIDE > EPI4 ? N_WAVES * WAVE_STRIDE : EPI4;    // small tile sets: the epilogue's need
+  // 8 accumulators per reduction chunk (half the rounds, each with two barriers) where the LDS allows it: the tile area
+  // grows to the chunk buffer's need when that still fits UPD16_LDS_MAX (mlp_impl.h) and the layout already holds more
+  // than half of it (one workgroup per CU either way); 4 otherwise
+  static constexpr int LDS_CAP = (160 * 1024 - 256) / 4;
+  static constexpr int EPI4 = 1024 + N_WAVES * 4 * 256 + PMAX, EPI8 = 1024 + N_WAVES * 8 * 256 + PMAX;
+  static constexpr int TILE_AREA0 = N_WAVES * WAVE_STRIDE > EPI4 ? N_WAVES * WAVE_STRIDE : EPI4;   // small tile sets: the epilogue's need
+  static constexpr int TILE_AREA = TILE_AREA0 < EPI8 && TILES + EPI8 <= LDS_CAP && 2 * (TILES + TILE_AREA0) > LDS_CAP ? EPI8 : TILE_AREA0;
   static constexpr int TOTAL = TILES + TILE_AREA;
-  static constexpr int CH = (1024 + N_WAVES * 8 * 256 + PMAX <= TILE_AREA) ? 8 : 4;       // accumulators per reduction chunk
+  static constexpr int CH = (EPI8 <= TILE_AREA) ? 8 : 4;       // accumulators per reduction chunk
   static_assert(1024 + N_WAVES * CH * 256 + PMAX <= TILE_AREA, "epilogue buffers do not fit the tile area");
+  static_assert(TILES % 4 == 0, "the epilogue's chunk buffer and flat gradient are read and written 16 bytes at a time");
 };
 
 struct Upd16Args {
@@ -391,9 +397,11 @@ __device__ __forceinline__ float critic_loss16(float v, float vo, float ret, flo
 // workgroup's summed raw products in R:  G at R[wo + f K + k], db at R[bo + f] (f < F <= 8 NJ, k < K <= 64).
 //   R[wo..] <- gam[k] G + bet[k] db[f];  R[go + k] <- sum_f W[f][k] G[f][k];  R[to + k] <- sum_f W[f][k] db[f]
 // Thread (k = tid & 63, part = tid >> 6) owns rows f = part + 8 j; w[j] = W[f][k] (raw, preloaded from global memory).
+// affine_part16 does the in-place part and leaves the 8 partial sums of each column in scr[0, 1024); after a barrier
+// affine_sum16 (64 threads, k = tid & 63) adds them up in the same order.
 template <int NJ>
-__device__ __forceinline__ void affine_epilogue16(float *R, int wo, int bo, int F, int K, const float *gam, const float *bet,
-                                                  const float (&w)[NJ], int go, int to, float *scr) {
+__device__ __forceinline__ void affine_part16(float *R, int wo, int bo, int F, int K, const float *gam, const float *bet,
+                                              const float (&w)[NJ], float *scr) {
   const int k = threadIdx.x & 63, part = threadIdx.x >> 6;
   float sg = 0.f, sb = 0.f;
   if (k < K) {
@@ -412,14 +420,27 @@ __device__ __forceinline__ void affine_epilogue16(float *R, int wo, int bo, int 
   }
   scr[part * 64 + k] = sg;
   scr[512 + part * 64 + k] = sb;
-  __syncthreads();
-  if (threadIdx.x < 64 && k < K) {
+}
+__device__ __forceinline__ void affine_sum16(float *R, int go, int to, int K, const float *scr) {
+  const int k = threadIdx.x & 63;
+  if (k < K) {
     float a = 0.f, b = 0.f;
 #pragma unroll
     for (int pp = 0; pp < 8; ++pp) { a += scr[pp * 64 + k]; b += scr[512 + pp * 64 + k]; }
     R[go + k] = a; R[to + k] = b;
   }
-  __syncthreads();
+}
+
+// dst[0, n) <- src[0, n) (src == nullptr: zeros) by the whole workgroup: 16-byte stores when both ends allow them
+__device__ __forceinline__ void copy16(float *dst, const float *src, int n) {
+  int e0 = 0;
+  if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0) {
+    const int n4 = n >> 2;
+    for (int e = threadIdx.x; e < n4; e += blockDim.x)
+      st4(dst + 4 * e, src ? ld4(src + 4 * e) : f32x4{0.f, 0.f, 0.f, 0.f});
+    e0 = 4 * n4;
+  }
+  for (int e = e0 + threadIdx.x; e < n; e += blockDim.x) dst[e] = src ? src[e] : 0.f;
 }
 
 // Workgroup `bid` of the `nb` workgroups that share this network's rows.  512 threads (8 waves, 2 per SIMD).
@@ -673,18 +694,29 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
     // ---- layer 1 ----
 #pragma unroll
     for (int bo = 0; bo < 4; ++bo) xh[bo] = ld4(lds + M::B1 + 16 * bo + 4 * q);
+    // exactly C k-steps: the group's count nk (4, or C % 4 in the last group) picks one of four straight-line bodies, so
+    // there is one uniform branch per group, not one per k-step (each of which ended a basic block in front of the next
+    // group's LDS reads).  The k-steps left out (slots t >= C) multiply staged weights that are exactly zero (see the staging)
+    // with finite inputs (with the feature norm on, those slots hold -mean * rstd, not 0): every product is +-0, and adding it
+    // leaves a non-zero accumulator unchanged bit for bit.
 #pragma unroll
     for (int tc = 0; tc < NV / 4; ++tc) {
-      if (4 * tc < C) {
+      const int nk = C - 4 * tc;                                   // wave-uniform
+      if (nk > 0) {
         f32x4 a[4];
 #pragma unroll
         for (int bo = 0; bo < 4; ++bo) a[bo] = ld4(lds + M::W1 + ((bo * M::NT + tc) * 64 + lane) * 4);
-        // (all four k-steps of a started group: slots beyond C meet zero weights — up to 12 idle MFMAs per tile instead of
-        // a uniform branch per k-step, each of which ended a basic block in front of the next group's LDS reads)
+        auto ksteps = [&](auto kc) {
+          constexpr int K = decltype(kc)::value;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+          for (int i = 0; i < K; ++i)
 #pragma unroll
-          for (int bo = 0; bo < 4; ++bo) xh[bo] = mfma16(a[bo][i], x0[4 * tc + i], xh[bo]);
+            for (int bo = 0; bo < 4; ++bo) xh[bo] = mfma16(a[bo][i], x0[4 * tc + i], xh[bo]);
+        };
+        if (nk >= 4) ksteps(std::integral_constant<int, 4>{});
+        else if (nk == 3) ksteps(std::integral_constant<int, 3>{});
+        else if (nk == 2) ksteps(std::integral_constant<int, 2>{});
+        else ksteps(std::integral_constant<int, 1>{});
       }
     }
     }
@@ -913,48 +945,80 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
   }
   // ---- sum the waves' raw products (deterministic: fixed order, no atomics).  The accumulators (f32x4 per lane) go through
   // a [wave][CH][lane] buffer CH at a time, one 16-byte store each; wave w then sums accumulator 8 c + w of chunk c over the
-  // 8 source waves (16-byte reads) and scatters the four sums to the flat parameter layout in R0.
+  // 8 source waves (16-byte reads) and scatters the four sums to the flat parameter layout in R0.  The per-feature vectors
+  // {gB1, gB2, gBh, gWc} of every wave ride along as one more accumulator (id NACC), in the last round's spare slot.
   const int Pn = HEAD == 3 ? (o.gru_wih >= 0 ? o.gru_wih : o.wh) : o.total;      // trunk only: the parameters in front of the GRU / head
   constexpr int CH = M::CH;                                     // accumulators per chunk (8 | 4)
   float *cb = scr + 1024;                                       // chunk buffer: n_waves x CH x 256 floats
   const int rb = XL1 ? o.b1 : 0;                                // XL1: W1 / feature-norm gradients are not this kernel's
   float *R0 = cb + M::N_WAVES * CH * 256 - rb;                  // indexed by absolute flat offsets >= rb
-  constexpr int N1 = XL1 ? 0 : 4 * NBK, N2 = LN > 0 ? 16 : 0, NH = HEAD == 1 ? 4 : 0, NACC = N1 + N2 + NH;
+  constexpr int N1 = XL1 ? 0 : 4 * NBK, N2 = LN > 0 ? 16 : 0, NH = HEAD == 1 ? 4 : 0, NACC = N1 + N2 + NH, NR = NACC + 1;
+  f32x4 sv; sv[0] = gB1f; sv[1] = gB2f; sv[2] = gBhf; sv[3] = gWc;
   auto acc_of = [&](auto idc) -> f32x4 & {
     constexpr int id = decltype(idc)::value;
     if constexpr (id < N1) return gW1[id / NBK][id % NBK];
     else if constexpr (id < N1 + N2) return gW2[(id - N1) / 4][(id - N1) % 4];
-    else return gWh[0][id - N1 - N2];
+    else if constexpr (id < NACC) return gWh[0][id - N1 - N2];
+    else return sv;
   };
-  static_for16<(NACC + CH - 1) / CH>([&](auto cc) {
+  float lsum[M::N_WAVES * 4];
+  static_for16<(NR + CH - 1) / CH>([&](auto cc) {
     constexpr int c0 = decltype(cc)::value * CH;
     static_for16<CH>([&](auto jc) {
       constexpr int id = c0 + decltype(jc)::value;
-      if constexpr (id < NACC) st4(cb + ((wave * CH + (id - c0)) * 64 + lane) * 4, acc_of(std::integral_constant<int, id>{}));
+      if constexpr (id < NR) st4(cb + ((wave * CH + (id - c0)) * 64 + lane) * 4, acc_of(std::integral_constant<int, id>{}));
     });
     __syncthreads();
+    // the waves' loss sums into thread 0's registers: this barrier follows the scr[960..] writes, and the transform below
+    // does not touch scr
+    if constexpr (c0 + CH >= NR) {
+      if (threadIdx.x == 0) {
+#pragma unroll
+        for (int e = 0; e < M::N_WAVES * 4; ++e) lsum[e] = scr[960 + e];
+      }
+    }
     static_for16<CH>([&](auto jc) {
       constexpr int id = c0 + decltype(jc)::value;
-      if constexpr (id < NACC) {
+      if constexpr (id < NR) {
         if (wave == id - c0) {
           f32x4 t[M::N_WAVES];
 #pragma unroll
           for (int sw = 0; sw < M::N_WAVES; ++sw) t[sw] = ld4(cb + ((sw * CH + (id - c0)) * 64 + lane) * 4);
-          f32x4 v = t[0];
+          if constexpr (id == NACC) {
+            // lane = feature; component 0 gB1 | 1 gB2 | 2 gBh (trunk: d gamma) | 3 gWc (trunk: d beta)
+            float v[4];
 #pragma unroll
-          for (int sw = 1; sw < M::N_WAVES; ++sw) { v[0] += t[sw][0]; v[1] += t[sw][1]; v[2] += t[sw][2]; v[3] += t[sw][3]; }
+            for (int i = 0; i < 4; ++i) {
+              v[i] = 0.f;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            if constexpr (id < N1) {
-              const int f = 16 * (id / NBK) + 4 * q + i, kc = 16 * (id % NBK) + n;      // tile column q' NV + t
-              const int tq = kc / NV, tt = kc % NV, k = tq * C + tt;
-              if (tt < C && k < D) R0[o.w1 + f * D + k] = v[i];
-            } else if constexpr (id < N1 + N2) {
-              const int f = 16 * ((id - N1) / 4) + 4 * q + i, k = 16 * ((id - N1) % 4) + n;
-              R0[o.w2[0] + f * HID + k] = v[i];
+              for (int sw = 0; sw < M::N_WAVES; ++sw) v[i] += t[sw][i];
+            }
+            R0[o.b1 + lane] = v[0];
+            if constexpr (LN > 0) R0[o.b2[0] + lane] = v[1];
+            if constexpr (HEAD == 3) {
+              R0[(LN > 0 ? o.ln2_w[0] : o.ln1_w) + lane] = v[2];
+              R0[(LN > 0 ? o.ln2_b[0] : o.ln1_b) + lane] = v[3];
             } else {
-              const int a = 4 * q + i, k = 16 * (id - N1 - N2) + n;
-              if (a < A) R0[o.wh + a * HID + k] = v[i];
+              if (HEAD == 1 ? lane < A : lane == 0) R0[o.bh + lane] = v[2];
+              if constexpr (HEAD == 2) R0[o.wh + lane] = v[3];
+            }
+          } else {
+            f32x4 v = t[0];
+#pragma unroll
+            for (int sw = 1; sw < M::N_WAVES; ++sw) { v[0] += t[sw][0]; v[1] += t[sw][1]; v[2] += t[sw][2]; v[3] += t[sw][3]; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              if constexpr (id < N1) {
+                const int f = 16 * (id / NBK) + 4 * q + i, kc = 16 * (id % NBK) + n;      // tile column q' NV + t
+                const int tq = kc / NV, tt = kc % NV, k = tq * C + tt;
+                if (tt < C && k < D) R0[o.w1 + f * D + k] = v[i];
+              } else if constexpr (id < N1 + N2) {
+                const int f = 16 * ((id - N1) / 4) + 4 * q + i, k = 16 * ((id - N1) % 4) + n;
+                R0[o.w2[0] + f * HID + k] = v[i];
+              } else {
+                const int a = 4 * q + i, k = 16 * (id - N1 - N2) + n;
+                if (a < A) R0[o.wh + a * HID + k] = v[i];
+              }
             }
           }
         }
@@ -962,51 +1026,26 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
     });
     __syncthreads();
   });
-  STAMP(18);  // accumulator chunks
-  float lsum[M::N_WAVES * 4];
-  // per-feature vectors: {gB1, gB2, gBh, gWc} of every wave, wave w < 4 sums component w
-  {
-    f32x4 sv; sv[0] = gB1f; sv[1] = gB2f; sv[2] = gBhf; sv[3] = gWc;
-    st4(cb + (wave * 64 + lane) * 4, sv);
-    __syncthreads();
-    // the waves' loss sums into thread 0's registers HERE: behind a barrier that every instantiation executes after the
-    // scr[960..] writes (the accumulator-chunk loop above has ZERO trips when the kernel owns no MFMA accumulators — wide
-    // critic, layer_N = 0 — so its barriers cannot be relied on), and in front of the barrier below, after which
-    // affine_epilogue16 reuses scr[0, 1024) as scratch (read any later, the eighth wave's scratch writes raced with this
-    // read: the value-loss statistic of a workgroup came out short now and then — the gradients never go through this slot)
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int e = 0; e < M::N_WAVES * 4; ++e) lsum[e] = scr[960 + e];
-    }
-    if (wave < 4) {
-      float v = 0.f;
-#pragma unroll
-      for (int sw = 0; sw < UPD16_THREADS / WAVE; ++sw) v += cb[(sw * 64 + lane) * 4 + wave];
-      if (wave == 0) R0[o.b1 + lane] = v;
-      if (wave == 1) { if constexpr (LN > 0) R0[o.b2[0] + lane] = v; }
-      if (wave == 2) {
-        if constexpr (HEAD == 3) R0[(LN > 0 ? o.ln2_w[0] : o.ln1_w) + lane] = v;
-        else if (HEAD == 1 ? lane < A : lane == 0) R0[o.bh + lane] = v;
-      }
-      if (wave == 3) {
-        if constexpr (HEAD == 2) R0[o.wh + lane] = v;
-        if constexpr (HEAD == 3) R0[(LN > 0 ? o.ln2_b[0] : o.ln1_b) + lane] = v;
-      }
-    }
-    __syncthreads();
-  }
-  STAMP(14);  // cross-wave reduction
-  // ---- raw products -> gradients (LayerNorm affines of the consumers' inputs), all threads ----
+  STAMP(18);  // accumulator chunks + vector sums
+  // ---- raw products -> gradients (LayerNorm affines of the consumers' inputs), all threads, ONE barrier pair: the three
+  // matrices' transforms touch disjoint ranges of R0, each keeps its partial sums in its own part of the (free) chunk buffer ----
   {
     const int gl = LN > 0 ? M::G2 : M::G1, tl = LN > 0 ? M::T2 : M::T1;
     const int ogl = LN > 0 ? o.ln2_w[0] : o.ln1_w, otl = LN > 0 ? o.ln2_b[0] : o.ln1_b;
-    if constexpr (HEAD != 3) affine_epilogue16<NJH>(R0, o.wh, o.bh, A, HID, lds + gl, lds + tl, ewh, ogl, otl, scr);
-    if constexpr (LN > 0) affine_epilogue16<8>(R0, o.w2[0], o.b2[0], HID, HID, lds + M::G1, lds + M::T1, ew2, o.ln1_w, o.ln1_b, scr);
-    if (fnorm && !XL1) affine_epilogue16<8>(R0, o.w1, o.b1, HID, D, lds + M::FN_W, lds + M::FN_B, ew1, o.fn_w, o.fn_b, scr);
+    const bool t1 = fnorm && !XL1;
+    if constexpr (HEAD != 3) affine_part16<NJH>(R0, o.wh, o.bh, A, HID, lds + gl, lds + tl, ewh, cb);
+    if constexpr (LN > 0) affine_part16<8>(R0, o.w2[0], o.b2[0], HID, HID, lds + M::G1, lds + M::T1, ew2, cb + 1024);
+    if (t1) affine_part16<8>(R0, o.w1, o.b1, HID, D, lds + M::FN_W, lds + M::FN_B, ew1, cb + 2048);
+    __syncthreads();
+    const int part = threadIdx.x >> 6;
+    if (HEAD != 3 && part == 0) affine_sum16(R0, ogl, otl, HID, cb);
+    if (LN > 0 && part == 1) affine_sum16(R0, o.ln1_w, o.ln1_b, HID, cb + 1024);
+    if (t1 && part == 2) affine_sum16(R0, o.fn_w, o.fn_b, D, cb + 2048);
+    __syncthreads();
   }
   STAMP(15);  // raw -> gradient transform
   float *slab = p.slabs + (size_t)bid * p.slab_stride + p.slab_col0;
-  for (int e = rb + threadIdx.x; e < Pn; e += blockDim.x) slab[e] = R0[e];
+  copy16(slab + rb, R0 + rb, Pn - rb);
   if (HEAD != 3 && threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1017,10 +1056,11 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
   }
   STAMP(16);  // slab write + loss partials
   STAMP_FLUSH();
+  STAMP_FLUSH_WAVES(HEAD);                                      // (the tag says which network's row: scripts/stamps_dual.py)
   // ---- rows of the other network that none of its workgroups writes (dual launch, unequal shares) ----
   if (bid >= P.zero_row0 && bid < P.zero_row1) {
     float *zs = p.slabs + (size_t)bid * p.slab_stride + P.zero_col0;
-    for (int e = threadIdx.x; e < P.zero_cols; e += blockDim.x) zs[e] = 0.f;
+    copy16(zs, nullptr, P.zero_cols);
     if (threadIdx.x < 4 && P.zero_partials && !p.cfg.accumulate_partials) P.zero_partials[(size_t)bid * 4 + threadIdx.x] = 0.0;
   }
 }
