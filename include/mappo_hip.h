@@ -262,7 +262,8 @@ int mappo_critic_update(const float *params, const mappo_net_desc *desc /*host*/
  * by side on disjoint CUs (shares proportional to their per-tile cost); each writes its own slab columns and loss partials.
  * mappo_dual_update_slabs = the slab rows / partial rows the caller provides PER NETWORK: every one of them is written by
  * the launch (a network with fewer workgroups has its remaining rows zero-filled), so the reduction runs over that count.
- * layer_N <= 1 and out_dim <= 16 take the one-wave-per-16-sample-tile kernel (csrc/mlp_upd16.h), the rest the pair kernel. */
+ * layer_N <= 1 and out_dim <= 16 take the one-wave-per-16-sample-tile kernel (csrc/mlp_upd16.h), the rest the pair kernel
+ * (so does an actor with 33..64 inputs and layer_N = 1, whose 16-sample-tile layout does not fit the LDS). */
 int32_t mappo_dual_update_slabs(const mappo_net_desc *actor_desc /*host*/, const mappo_net_desc *critic_desc /*host*/, int64_t B);
 int mappo_actor_critic_update(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *obs,
                               const float *critic_params, const mappo_net_desc *critic_desc /*host*/, const float *share_obs,

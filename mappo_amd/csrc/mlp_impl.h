@@ -2282,8 +2282,20 @@ extern "C" int mappo_actor_act(const float *params, const mappo_net_desc *desc, 
 
 // ---- one wave per 16-sample tile (mlp_upd16.h) ---------------------------------------------------------------------
 #define UPD16_WAVES (UPD16_THREADS / WAVE)
+static size_t upd16_lds_floats(const mappo_net_desc &d, bool actor) {
+  const bool w = d.in_dim > 32;
+  if (actor) {
+    if (d.layer_N > 0) return w ? L16<1, 1, true>::TOTAL : L16<1, 1, false>::TOTAL;
+    return w ? L16<0, 1, true>::TOTAL : L16<0, 1, false>::TOTAL;
+  }
+  if (d.layer_N > 0) return w ? L16<1, 2, true>::TOTAL : L16<1, 2, false>::TOTAL;
+  return w ? L16<0, 2, true>::TOTAL : L16<0, 2, false>::TOTAL;
+}
+// The layout must also fit: L16<1, 1, true> (actor, 33..64 inputs, layer_N = 1) needs 171 072 B > UPD16_LDS_MAX, so that actor
+// takes the pair kernel (mlp_upd2.h), in the single and in the dual launch.
 static bool upd16_eligible(const mappo_net_desc &d, bool actor) {
-  return d.in_dim <= MAXD && d.layer_N <= 1 && !d.recurrent && (actor ? d.out_dim <= 16 : d.out_dim == 1);
+  return d.in_dim <= MAXD && d.layer_N <= 1 && !d.recurrent && (actor ? d.out_dim <= 16 : d.out_dim == 1) &&
+         upd16_lds_floats(d, actor) * sizeof(float) <= UPD16_LDS_MAX;
 }
 // MFMA instructions per 16-sample tile (+ a flat allowance for the VALU phases): the share of the chip a network gets
 static int upd16_tile_cost(const mappo_net_desc &d, bool actor) {
@@ -2302,15 +2314,6 @@ static size_t upd16_trunk_lds_floats(const mappo_net_desc &d) {
   const bool w = d.in_dim > 32;
   if (d.layer_N > 0) return w ? L16<1, 3, true>::TOTAL : L16<1, 3, false>::TOTAL;
   return w ? L16<0, 3, true>::TOTAL : L16<0, 3, false>::TOTAL;
-}
-static size_t upd16_lds_floats(const mappo_net_desc &d, bool actor) {
-  const bool w = d.in_dim > 32;
-  if (actor) {
-    if (d.layer_N > 0) return w ? L16<1, 1, true>::TOTAL : L16<1, 1, false>::TOTAL;
-    return w ? L16<0, 1, true>::TOTAL : L16<0, 1, false>::TOTAL;
-  }
-  if (d.layer_N > 0) return w ? L16<1, 2, true>::TOTAL : L16<1, 2, false>::TOTAL;
-  return w ? L16<0, 2, true>::TOTAL : L16<0, 2, false>::TOTAL;
 }
 static int prep16(Upd16Args &a, bool actor, const char *who) {
   UpdArgs &u = a.u;

@@ -552,13 +552,11 @@ class PolicyRef:
                                                  eps=args.opti_eps, weight_decay=args.weight_decay)
 
 
-def ppo_update_ref(args, policy, vnorm, sample, update_actor=True):
-    """r_mappo.py:91-164 on torch-CPU autograd.  Returns the 6-tuple as floats + imp_weights."""
-    t = lambda x: torch.as_tensor(x, dtype=torch.float32)
-    (share_obs, obs, rnn_a, rnn_c, actions, v_old, ret, masks, active, old_logp, adv, avail) = \
-        [None if x is None else t(x) for x in sample]
-    logp, ent, _ = policy.actor.evaluate_actions(obs, rnn_a, actions, masks, avail, active)
-    values, _ = policy.critic(share_obs, rnn_c, masks)
+def ppo_losses_ref(args, logp, ent, values, old_logp, adv, active, v_old, tgt):
+    """The loss expressions of r_mappo.py:52-141 on autograd tensors (any float dtype): evaluate_actions' log-probs and
+    entropy, the critic's values and the value target (already normalised under use_valuenorm).  Honours every loss flag
+    of `args`.  Returns (policy_loss, value_loss, imp_weights); the actor objective is policy_loss - entropy_coef * ent,
+    the critic's value_loss * value_loss_coef."""
     imp = torch.exp(logp - old_logp)
     s1 = imp * adv
     s2 = torch.clamp(imp, 1.0 - args.clip_param, 1.0 + args.clip_param) * adv
@@ -567,6 +565,32 @@ def ppo_update_ref(args, policy, vnorm, sample, update_actor=True):
         policy_loss = (-surr * active).sum() / active.sum()
     else:
         policy_loss = -surr.mean()
+    v_clip = v_old + (values - v_old).clamp(-args.clip_param, args.clip_param)
+    e_c, e_o = tgt - v_clip, tgt - values
+    if args.use_huber_loss:
+        l_c, l_o = huber_ref(e_c, args.huber_delta), huber_ref(e_o, args.huber_delta)
+    else:
+        l_c, l_o = e_c ** 2 / 2, e_o ** 2 / 2
+    l = torch.max(l_o, l_c) if args.use_clipped_value_loss else l_o
+    value_loss = (l * active).sum() / active.sum() if args.use_value_active_masks else l.mean()
+    return policy_loss, value_loss, imp
+
+
+def ppo_update_ref(args, policy, vnorm, sample, update_actor=True, dtype=torch.float32):
+    """r_mappo.py:91-164 on torch-CPU autograd.  Returns the 6-tuple as floats + imp_weights.  `dtype` is that of the
+    sample tensors; the caller converts the policy's networks to it (float64: a reference for the fp32 kernels).  The
+    ValueNorm statistics stay float32, as in the reference."""
+    t = lambda x: torch.as_tensor(x, dtype=dtype)
+    (share_obs, obs, rnn_a, rnn_c, actions, v_old, ret, masks, active, old_logp, adv, avail) = \
+        [None if x is None else t(x) for x in sample]
+    logp, ent, _ = policy.actor.evaluate_actions(obs, rnn_a, actions, masks, avail, active)
+    values, _ = policy.critic(share_obs, rnn_c, masks)
+    if args.use_valuenorm:
+        vnorm.update(ret)
+        tgt = vnorm.normalize(ret).to(dtype)
+    else:
+        tgt = ret
+    policy_loss, value_loss, imp = ppo_losses_ref(args, logp, ent, values, old_logp, adv, active, v_old, tgt)
     policy.actor_optimizer.zero_grad()
     if update_actor:
         (policy_loss - ent * args.entropy_coef).backward()
@@ -576,19 +600,6 @@ def ppo_update_ref(args, policy, vnorm, sample, update_actor=True):
         a_norm = math.sqrt(sum(float(p.grad.norm()) ** 2 for p in policy.actor.parameters() if p.grad is not None))
     policy.actor_optimizer.step()
     # critic (r_mappo.py:52-89)
-    v_clip = v_old + (values - v_old).clamp(-args.clip_param, args.clip_param)
-    if args.use_valuenorm:
-        vnorm.update(ret)
-        tgt = vnorm.normalize(ret)
-    else:
-        tgt = ret
-    e_c, e_o = tgt - v_clip, tgt - values
-    if args.use_huber_loss:
-        l_c, l_o = huber_ref(e_c, args.huber_delta), huber_ref(e_o, args.huber_delta)
-    else:
-        l_c, l_o = e_c ** 2 / 2, e_o ** 2 / 2
-    l = torch.max(l_o, l_c) if args.use_clipped_value_loss else l_o
-    value_loss = (l * active).sum() / active.sum() if args.use_value_active_masks else l.mean()
     policy.critic_optimizer.zero_grad()
     (value_loss * args.value_loss_coef).backward()
     if args.use_max_grad_norm:

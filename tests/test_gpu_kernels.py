@@ -490,7 +490,8 @@ def _relu_margin(net, x):
 def _loss_margin(a, actor, critic, obs, sobs, actions, avail, active, old_logp, v_old, ret, vn):
     """Distance per row (float64 oracle networks) to the non-smooth points of the PPO and value losses (r_mappo.py:91-141): the
     ratio at 1 -/+ clip_param, |value - old value| at clip_param, and the two Huber losses of the clipped value loss equal while
-    the value is clipped.  The gradient jumps by one sample's worth across each of them."""
+    the value is clipped.  The gradient jumps by one sample's worth across each of them.  The loss flags of `a` decide which
+    kinks exist: none of the value clip's without use_clipped_value_loss (the Huber loss itself has a continuous slope)."""
     import copy
     t = lambda x: torch.from_numpy(x).double()
     ad, cd = copy.deepcopy(actor).double(), copy.deepcopy(critic).double()
@@ -500,11 +501,14 @@ def _loss_margin(a, actor, critic, obs, sobs, actions, avail, active, old_logp, 
     c = a.clip_param
     imp = torch.exp(lp - t(old_logp).view(-1, 1))
     m_ratio = torch.minimum((imp - (1 - c)).abs(), (imp - (1 + c)).abs())
+    if not a.use_clipped_value_loss:
+        return m_ratio.view(-1).numpy()
     vo = t(v_old).view(-1, 1)
     d = vals - vo
-    tgt = vn.normalize(t(ret).view(-1, 1)).double()
+    tgt = vn.normalize(t(ret).view(-1, 1)).double() if a.use_valuenorm else t(ret).view(-1, 1)
     vclip = vo + d.clamp(-c, c)
-    gap = (O.huber_ref(tgt - vals, a.huber_delta) - O.huber_ref(tgt - vclip, a.huber_delta)).abs()
+    loss = (lambda e: O.huber_ref(e, a.huber_delta)) if a.use_huber_loss else (lambda e: e * e / 2)
+    gap = (loss(tgt - vals) - loss(tgt - vclip)).abs()
     m_max = torch.where(d.abs() > c, gap, torch.full_like(gap, np.inf))
     return torch.minimum(torch.minimum(m_ratio, (d.abs() - c).abs()), m_max).view(-1).numpy()
 

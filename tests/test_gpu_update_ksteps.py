@@ -16,7 +16,7 @@ def _c_mod4(d):
 
 
 # (actor in_dim, critic in_dim): actor narrow C % 4 = 0, 1, 2, 3 | critic wide C % 4 = 3, 2, 0, 1 (an actor wider than 32
-# inputs does not fit the 16-sample-tile kernel's LDS and takes the pair kernel)
+# inputs with layer_N = 1 does not fit the 16-sample-tile kernel's LDS and takes the pair kernel: test_gpu_update_matrix.py)
 KSTEP_CASES = [(13, 44, 5, True, 333, True), (17, 54, 5, True, 1001, False), (22, 61, 9, False, 517, True),
                (26, 33, 3, True, 250, False), (18, 64, 5, True, 3072, True), (30, 54, 16, False, 129, False),
                (25, 21, 7, True, 495, False), (10, 14, 2, False, 17, True)]
