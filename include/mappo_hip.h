@@ -408,6 +408,24 @@ int mappo_mpe_spread_reset(double *agent_pos, double *agent_vel, double *landmar
 int mappo_mpe_spread_step(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *tstep, int64_t *episode,
                           const float *actions, int32_t action_mode, float *obs, float *rewards, uint8_t *dones, int32_t N, int32_t M,
                           int32_t L, int32_t episode_length, uint64_t seed, mappo_stream_t stream);
+/* One launch per rollout EPISODE on the environment above, env steps included (csrc/rollout_spread.h): what T x
+ * (mappo_rollout_step + mappo_mpe_spread_step with action_mode 1) + the bootstrap mappo_rollout_step do, bit for bit
+ * (mpe_runner.py:22-40,95-139 collect / env.step / insert; core.py:207-322, simple_spread.py:32-103, environment.py:117-256 the step).
+ * Per step t < T: actor on the observation rows of step t (step 0: obs_buf slot 0) with counter + t (+ *counter_dev) and row
+ * index n*M + m -> actions / logp [T][B]; the environments step in float64 on the sampled indices from the state in agent_pos /
+ * agent_vel / landmark_pos / tstep / episode (reset-on-done after env_episode_length steps, Philox stream (env_seed, episode, n));
+ * obs -> obs_buf / share_buf slot t + 1 ([T+1][B][in_dim]), rewards -> rew_buf [T][B] slot t, 1 - done -> mask_buf [T+1][B] slot
+ * t + 1.  Critic on the share rows of step t <= T -> values [T][B], step T -> next_values [B].  The five state arrays are stored
+ * back at the end, so the environment continues in either path.  B = N*M rows; M, L <= 8; actor in_dim = 4 + 2L + 4(M-1), out_dim 5;
+ * critic in_dim = M * in_dim (centralized) or in_dim; both <= 64, same layer_N and activation; not recurrent; no available
+ * actions.  Validates on the host before the launch. */
+int mappo_rollout_episode_spread(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *critic_params,
+                                 const mappo_net_desc *critic_desc /*host*/, int32_t T, int32_t N, int32_t M, int32_t L,
+                                 int32_t env_episode_length, uint64_t env_seed, double *agent_pos, double *agent_vel,
+                                 double *landmark_pos, int32_t *tstep, int64_t *episode, int32_t deterministic, uint64_t seed,
+                                 uint64_t counter, const uint64_t *counter_dev, float *obs_buf, float *share_buf, float *rew_buf,
+                                 float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/, float *values /*[T][B]*/,
+                                 float *next_values /*[B]*/, int32_t centralized, mappo_stream_t stream);
 
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only

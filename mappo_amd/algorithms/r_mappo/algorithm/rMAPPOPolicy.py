@@ -217,6 +217,25 @@ class R_MAPPOPolicy:
                             b.action_log_probs, b.value_preds, next_values, centralized)
         return next_values
 
+    @torch.no_grad()
+    def collect_episode_env_fused(self, buffer, env_state, next_values, centralized=True, deterministic=False):
+        """A whole rollout episode on the GPU-resident simple_spread env in one launch, env steps included
+        (mappo_rollout_episode_spread): `env_state` = SimpleSpreadVecEnv.episode_state().  Writes what T x (collect_step_fused +
+        env.step) + the bootstrap call write — buffer.{actions, action_log_probs, value_preds}[0..T-1], obs / share_obs / masks
+        [1..T], rewards [0..T-1], the critic of step T into `next_values` [N*M] — and leaves the env's state where T steps leave it.
+        Step t samples with counter t + *_counter_dev, as the stepwise path does."""
+        b, st = buffer, env_state
+        T, N, M = b.episode_length, b.n_rollout_threads, b.num_agents
+        if (st["N"], st["M"]) != (N, M) or st["agent_pos"].device != self.device:
+            raise ValueError("collect_episode_env_fused: the env does not match the buffer (threads / agents / device)")
+        if not all(t.is_contiguous() for t in (b.obs, b.share_obs, b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds)):
+            raise ValueError("collect_episode_env_fused: the buffer does not have the device layout mappo_rollout_episode_spread writes")
+        ops.rollout_episode_spread(self.actor.flat, self.actor.desc, self.critic.flat, self.critic.desc, T, N, M, st["L"], st["T"],
+                                   st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"], st["tstep"], st["episode"],
+                                   deterministic, self.actor._seed, 0, self.actor._counter_dev, b.obs, b.share_obs, b.rewards, b.masks,
+                                   b.actions, b.action_log_probs, b.value_preds, next_values, centralized)
+        return next_values
+
     # ---- recurrent policies, SMAC-style envs: insert of the previous env output + this step's get_actions in one launch ----
     def can_fuse_recurrent_step(self, n_rows):
         from mappo_amd import recurrent

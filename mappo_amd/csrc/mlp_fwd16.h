@@ -169,10 +169,13 @@ __device__ __forceinline__ void head16r_load(Head16R<MODE> &hd, const float *P, 
 // results do not depend on which launch computes them.  DRAIN (episode kernel): wait for every load in flight — the next step's
 // rows, requested before this step's math — in front of the stores.  The stores sit in a divergent branch, so behind them the
 // counter can only be drained whole: the next step's wait for its rows would also wait for this step's stores to complete.
-template <bool RELU, int LN, int MODE, bool DRAIN = false>
+// ACT_TILE (MODE 1, the episode kernel that steps its environments itself): the action of tile row j also goes to act_tile[j]
+// in LDS, where the wave's environment lanes pick it up behind the closing wave_lds_sync.
+template <bool RELU, int LN, int MODE, bool DRAIN = false, bool ACT_TILE = false>
 __device__ __forceinline__ void tile16r_step(const FwdArgs &p, const Trunk16R<LN> &tw, const Head16R<MODE> &hd, f32x4 (&x)[4],
                                              float *out, float *actions, float *logp, uint64_t ctr_base, const uint64_t *ctr_dev,
-                                             float *tZ, const int64_t i, const bool ok, const int j, const int q) {
+                                             float *tZ, const int64_t i, const bool ok, const int j, const int q,
+                                             float *act_tile = nullptr) {
   constexpr int NBH = Head16R<MODE>::NBH;
   const int D = p.desc.in_dim, A = p.desc.out_dim;
   const bool fnorm = p.desc.use_feature_norm != 0;
@@ -217,6 +220,7 @@ __device__ __forceinline__ void tile16r_step(const FwdArgs &p, const Trunk16R<LN
         categorical_act_lane(tZ + j * TP, A, p.avail ? p.avail + i * A : nullptr, p.deterministic != 0, p.seed, ctr, (uint64_t)i, action, lp);
         actions[i] = action;
         logp[i] = lp;
+        if constexpr (ACT_TILE) act_tile[j] = action;
       }
       wave_lds_sync();
     }

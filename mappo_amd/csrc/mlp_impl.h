@@ -1763,7 +1763,7 @@ int upd16x_inst(int head, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s
 template int upd16x_inst<MLP_UPD_RELU, MLP_UPD_LN>(int, dim3, dim3, size_t, hipStream_t, const Upd16Args &);
 #endif
 
-#if defined(MLP_TU_MAIN) || defined(MLP_TU_STEP)
+#if defined(MLP_TU_MAIN) || defined(MLP_TU_STEP) || defined(MLP_TU_SPREAD)
 // LDS map, layer-1 arguments and launch shape of the one-launch wide forward (mlp_wide16.h) for the network in `a` (a.off / a.map set)
 static int wide_forward_prepare(FwdArgs &a, Wide16Args &w, size_t &lb, dim3 &grid, dim3 &block, bool &small, const char *who) {
   a.map.wave_stride = 16 * TP;                                   // the tail only needs the [16][TP] logits tile of a wave
@@ -2167,6 +2167,10 @@ extern "C" int mappo_rollout_episode(const float *actor_params, const mappo_net_
   MAPPO_CHECK_LAUNCH("rollout_episode");
   return MAPPO_OK;
 }
+#endif
+
+#ifdef MLP_TU_SPREAD
+#include "rollout_spread.h"
 #endif
 
 #ifdef MLP_TU_MAIN

@@ -48,6 +48,13 @@ class SimpleSpreadVecEnv:
         self.landmark_pos.copy_(torch.as_tensor(landmark_pos, dtype=torch.float64))
         self.tstep.fill_(int(tstep))
 
+    def episode_state(self):
+        """The capability behind the runner's one-launch episode on THIS env (mappo_rollout_episode_spread steps the environments
+        inside the rollout kernel): the five state tensors, which that launch reads and stores back, and what it needs to step
+        them.  (SyntheticMPEEnv.episode_block is the other such capability: an episode of env output that ignores the actions.)"""
+        return dict(agent_pos=self.agent_pos, agent_vel=self.agent_vel, landmark_pos=self.landmark_pos, tstep=self.tstep,
+                    episode=self.episode, N=self.N, M=self.M, L=self.L, T=self.T, seed=self.seed)
+
     def reset(self):
         obs = self._out[self._k][0]
         ops.mpe_spread_reset(self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep, self.episode, obs, self.N, self.M, self.L,

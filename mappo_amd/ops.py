@@ -286,6 +286,24 @@ def rollout_episode(actor_params, actor_desc, critic_params, critic_desc, obs, r
     _lib.check(rc, "mappo_rollout_episode")
 
 
+def rollout_episode_spread(actor_params, actor_desc, critic_params, critic_desc, T, N, M, L, env_episode_length, env_seed, agent_pos,
+                           agent_vel, landmark_pos, tstep, episode, deterministic, seed, counter, counter_dev, obs_buf, share_buf,
+                           rew_buf, mask_buf, actions, logp, values, next_values, centralized):
+    """A whole rollout episode on the GPU-resident simple_spread env in one launch, env steps included
+    (mappo_rollout_episode_spread): the five env state tensors (SimpleSpreadVecEnv) are read, stepped T times on the sampled
+    actions and stored back; the buffer arrays are the contiguous SharedReplayBuffer tensors, as for rollout_episode."""
+    f64 = torch.float64
+    rc = _lib.load().mappo_rollout_episode_spread(_ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), int(T),
+                                                  int(N), int(M), int(L), int(env_episode_length), int(env_seed) & (2 ** 64 - 1),
+                                                  _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
+                                                  _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(bool(deterministic)),
+                                                  int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
+                                                  _ptr(counter_dev, torch.int64, allow_none=True), _ptr(obs_buf), _ptr(share_buf),
+                                                  _ptr(rew_buf), _ptr(mask_buf), _ptr(actions), _ptr(logp), _ptr(values), _ptr(next_values),
+                                                  int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode_spread")
+
+
 def mlp_backward_slabs(B):
     return int(_lib.load().mappo_mlp_backward_slabs(int(B)))
 

@@ -79,6 +79,17 @@ class MPERunner(Runner):
             self.trainer.prep_rollout()
             b.compute_returns(nv, self.trainer.value_normalizer)
             return infos
+        if fuse and self._fuse_episode and self._episode_state_env() and self.trainer.policy.can_fuse_episode():
+            # the env's state lives on the device and its step is a device function: the episode, env steps included, is ONE
+            # launch (mappo_rollout_episode_spread), same buffer contents and env state as the stepwise loop below
+            b = self.buffer
+            if self._next_values is None:
+                self._next_values = torch.empty(b.n_rollout_threads * b.num_agents, device=b.device)
+            nv = self.trainer.policy.collect_episode_env_fused(b, self.envs.episode_state(), self._next_values, self.use_centralized_V)
+            b.step = 0
+            self.trainer.prep_rollout()
+            b.compute_returns(nv, self.trainer.value_normalizer)
+            return infos
         pending = None                     # env output of the previous step, not yet in the buffer (fused path)
         for step in range(self.episode_length):
             if fuse:
@@ -133,6 +144,18 @@ class MPERunner(Runner):
         if dev.type == "cuda" and dev.index is None:            # where its tensors land
             dev = torch.device("cuda", torch.cuda.current_device())
         return dev == self.trainer.policy.device
+
+    def _episode_state_env(self):
+        """The env steps inside the rollout kernel (SimpleSpreadVecEnv.episode_state): device state on the policy's device, no host
+        staging, and the observation / action shapes mappo_rollout_episode_spread is built for."""
+        env = self.envs
+        if not hasattr(env, "episode_state") or self._staging is not None:
+            return False
+        dev = torch.device(env.device)
+        if dev.type == "cuda" and dev.index is None:            # where its tensors land
+            dev = torch.device("cuda", torch.cuda.current_device())
+        a = self.trainer.policy.actor.desc
+        return dev == self.trainer.policy.device and a.in_dim == env.obs_dim and a.out_dim == 5
 
     def rollout(self):
         """T x (collect, env.step, insert) + compute().  With a vec-env that declares `graph_safe` (device-resident,
