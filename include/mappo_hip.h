@@ -351,7 +351,12 @@ int mappo_trunk_backward(const float *params, const mappo_net_desc *desc /*host*
  *                            mappo_trunk_backward with dxT)
  * scratch: mappo_gru16_scratch_floats(L, Nc) floats, [6][L][ceil(Nc/16)][4][64 lanes][4]: component c, step t, tile j, feature
  * block b; lane (n, q) holds features 16 b + 4 q + 0..3 of sequence 16 j + n (one contiguous KiB per wave access).  A blocked
- * feature array (x, d x) is one such component: mappo_gru16_blocked_floats(L, Nc).  mappo_gru16_slabs: slab rows written. */
+ * feature array (x, d x) is one such component: mappo_gru16_blocked_floats(L, Nc).  mappo_gru16_slabs: slab rows written.
+ * Write contract (tests/test_gpu_gru_matrix.py): each slab-writing kernel of the chain (the head kernel or the unsplit forward;
+ * wgrad; the trunk backward — the split recurrence kernels write no slab row) writes its own columns of ONE slab row per workgroup
+ * of its own grid (the grids differ; none exceeds mappo_gru16_slabs(L, Nc)) and zero-fills nothing, so rows [0, mappo_gru16_slabs)
+ * of the network's column range must be zero beforehand; the partials are [forward grid][4], the forward grid being that of the
+ * head kernel (split recurrence) or of the sequence kernel (unsplit) — at most mappo_gru16_slabs rows as well. */
 int64_t mappo_gru16_scratch_floats(int32_t L, int32_t Nc);
 int64_t mappo_gru16_blocked_floats(int32_t L, int32_t Nc);
 int32_t mappo_gru16_slabs(int32_t L, int32_t Nc);

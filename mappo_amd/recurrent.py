@@ -171,12 +171,19 @@ def _update_recurrent(tr, src, rows, h0_rows, L, Nc, update_actor, epochs=None):
     n_bwd = ops.gru16_slabs(L, Nc)                             # rows of loss partials / slab rows the 16-sequence-tile kernels may write
     n_slabs = max(n_trunk, n_bwd)
     P = pol.n_flat
-    slabs = tr._buf("slabs_rec", (n_slabs, P), zero=True)      # rows a kernel never writes stay zero
+    # Every kernel of the chain writes one slab row (and the forward one partial row) per workgroup of ITS OWN grid, and the
+    # grids differ per kernel and per (L, Nc); the reductions below run over n_slabs / n_bwd rows and rely on the rest being zero.
+    # So each (L, Nc) owns its arrays: a row one shape wrote is never summed by another (and captured graphs keep their addresses).
+    # Cost: one n_slabs x n_flat array (at most 256 rows) per distinct shape, kept for the trainer's life — train() on a buffer has
+    # one or two shapes; a caller of ppo_update with ever-changing sample shapes pays that per shape.
+    slabs = tr._buf(f"slabs_rec/{L}/{Nc}", (n_slabs, P), zero=True)
     if not update_actor and not tr._actor_slabs_clean:
-        slabs[:, :pol.seg_bounds[1]].zero_()
+        for (name, _, _), t in tr._ws.items():                 # every shape's array: the flag is one per trainer
+            if name.startswith("slabs_rec/"):
+                t[:, :pol.seg_bounds[1]].zero_()
     tr._actor_slabs_clean = not update_actor
-    pa = tr._buf("partials_a", (1024,), torch.float64, zero=True)
-    pc = tr._buf("partials_c", (1024,), torch.float64, zero=True)
+    pa = tr._buf(f"partials_a/{L}/{Nc}", (1024,), torch.float64, zero=True)
+    pc = tr._buf(f"partials_c/{L}/{Nc}", (1024,), torch.float64, zero=True)
     nets = []
     if update_actor:
         nets.append((pol.actor, src["obs"], src["h0_a"], 1, pa, 0, "actor"))
