@@ -177,6 +177,11 @@ int mappo_ppo_loss_fwd_bwd(const float *logits /*[B][A] minibatch order, pre-mas
 int mappo_mlp_forward(const float *params, const mappo_net_desc *desc /*host*/, const float *x /*[.][in_dim]*/,
                       const int32_t *rows /*[B] or NULL*/, int64_t B, float *out /*[B][out_dim]*/,
                       mappo_stream_t stream);
+/* Sampling contract (tests/rollout_ref.py restates it on the host): the draw of a row is Philox4x32-10 with key words {seed lo, seed hi}
+ * and counter words {row index lo, row index hi, counter lo, counter hi}; u = (output word 0 >> 8) * 2^-24, a 24-bit uniform in [0, 1).
+ * The action is the first a with u < p_0 + ... + p_a over the masked softmax (unavailable actions have p = 0); if rounding leaves u
+ * at or above the last sum, it is the last action with p > 0.  deterministic: the first maximum.  Every sampling entry point uses
+ * row index = the row's position in its [B] (per step of [T][B]) output, and counter + t (+ *counter_dev) for step t (t = 0 for one step). */
 int mappo_actor_act(const float *params, const mappo_net_desc *desc /*host*/, const float *obs,
                     const float *avail /*[B][A] or NULL*/, int64_t B, int32_t deterministic,
                     uint64_t seed, uint64_t counter, const uint64_t *counter_dev /*device word added to counter, or NULL*/,
