@@ -216,6 +216,10 @@ int mappo_rollout_episode(const float *actor_params, const mappo_net_desc *actor
                           uint64_t seed, uint64_t counter, const uint64_t *counter_dev, float *obs_buf, float *share_buf,
                           float *rew_buf, float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/,
                           float *values /*[T][B]*/, float *next_values /*[B]*/, int32_t centralized, mappo_stream_t stream);
+/* Which kernel body mappo_rollout_episode takes for this layer_N under the current environment: 1 = weights in LDS, several waves
+ * per SIMD (layer_N 0 / 1, the default), 0 = weights in registers (layer_N 2, MAPPO_EPISODE_LDS=0, or any of the register body's
+ * geometry overrides MAPPO_EPISODE_WAVES / _NET_WAVES / _INS_WAVES / _COST_A set without MAPPO_EPISODE_LDS). */
+int mappo_rollout_episode_uses_lds(int32_t layer_N);
 int32_t mappo_mlp_backward_slabs(int64_t B); /* number of slabs the launch below will write */
 int mappo_mlp_backward(const float *params, const mappo_net_desc *desc /*host*/, const float *x,
                        const int32_t *rows, int64_t B, const float *dout /*[B][out_dim]*/,

@@ -61,6 +61,7 @@ SIGNATURES = {
                                      _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I32, _P]),
     "mappo_rollout_episode": (C.c_int, [_P, C.POINTER(NetDesc), _P, C.POINTER(NetDesc), _I32, _I32, _I32, _P, _I64, _I64, _I64, _P, _I64,
                                         _I64, _I64, _P, _I64, _I64, _I64, _I32, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "mappo_rollout_episode_uses_lds": (C.c_int, [_I32]),
     "mappo_mlp_backward_slabs": (_I32, [_I64]),
     "mappo_mlp_backward": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _I64, _P, _P, _I64, _I64, _P, _P]),
     "mappo_wide_workspace_floats": (_I64, [_I64]),

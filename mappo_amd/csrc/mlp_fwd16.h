@@ -144,6 +144,9 @@ struct Head16R {
   static constexpr int NBH = MODE == 1 ? 2 : (MODE == 0 ? 1 : 0);     // head blocks of 16 outputs
   f32x4 wh[NBH > 0 ? NBH : 1][4];
   f32x4 bhv[NBH > 0 ? NBH : 1];
+  // tile16r_step reads the head through these accessors only (Head16L in mlp_ep16l.h: the same operands from LDS)
+  __device__ __forceinline__ f32x4 WH(int bo, int b) const { return wh[bo][b]; }
+  __device__ __forceinline__ f32x4 BH(int bo) const { return bhv[bo]; }
 };
 template <int MODE>
 __device__ __forceinline__ void head16r_load(Head16R<MODE> &hd, const float *P, const NetOff &o, int A, int j, int q) {
@@ -170,13 +173,15 @@ __device__ __forceinline__ void head16r_load(Head16R<MODE> &hd, const float *P, 
 // rows, requested before this step's math — in front of the stores.  The stores sit in a divergent branch, so behind them the
 // counter can only be drained whole: the next step's wait for its rows would also wait for this step's stores to complete.
 // ACT_TILE (MODE 1, the episode kernel that steps its environments itself): the action of tile row j also goes to act_tile[j]
-// in LDS, where the wave's environment lanes pick it up behind the closing wave_lds_sync.
-template <bool RELU, int LN, int MODE, bool DRAIN = false, bool ACT_TILE = false>
-__device__ __forceinline__ void tile16r_step(const FwdArgs &p, const Trunk16R<LN> &tw, const Head16R<MODE> &hd, f32x4 (&x)[4],
+// in LDS, where the wave's environment lanes pick it up behind the closing wave_lds_sync.  TW / HD: where the weights come from
+// (Trunk16R / Head16R: registers; Trunk16L / Head16L: LDS) — same operands, same order, same arithmetic.
+template <bool RELU, int LN, int MODE, bool DRAIN = false, bool ACT_TILE = false, class TW, class HD>
+__device__ __forceinline__ void tile16r_step(const FwdArgs &p, const TW &tw, const HD &hd, f32x4 (&x)[4],
                                              float *out, float *actions, float *logp, uint64_t ctr_base, const uint64_t *ctr_dev,
                                              float *tZ, const int64_t i, const bool ok, const int j, const int q,
                                              float *act_tile = nullptr) {
-  constexpr int NBH = Head16R<MODE>::NBH;
+  constexpr int NBH = HD::NBH;
+  static_assert(HD::NBH == Head16R<MODE>::NBH, "head blocks follow the mode");
   const int D = p.desc.in_dim, A = p.desc.out_dim;
   const bool fnorm = p.desc.use_feature_norm != 0;
   f32x4 h[4];
@@ -193,12 +198,14 @@ __device__ __forceinline__ void tile16r_step(const FwdArgs &p, const Trunk16R<LN
     f32x4 z[NBH > 0 ? NBH : 1];
 #pragma unroll
     for (int bo = 0; bo < NBH; ++bo) {
-      z[bo] = hd.bhv[bo];
+      z[bo] = hd.BH(bo);
       if (bo == 0 || A > 16) {
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
+        for (int b = 0; b < 4; ++b) {
+          const f32x4 a = hd.WH(bo, b);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) z[bo] = mfma16(hd.wh[bo][b][r], h[b][r], z[bo]);
+          for (int r = 0; r < 4; ++r) z[bo] = mfma16(a[r], h[b][r], z[bo]);
+        }
       }
     }
     if constexpr (DRAIN) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); }

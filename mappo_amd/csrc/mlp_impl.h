@@ -751,6 +751,7 @@ __global__ __launch_bounds__(256, 1) void rollout_episode_kernel(EpisodeArgs e) 
   else if (gw < e.wA + e.wC) episode16r_body<RELU, LN, 0>(e.c, e.sc, e.M, e.T + 1, e.T, e.next_values, tZ, gw - e.wA, e.wC);
   if (gw >= e.wI0 && gw < e.wAll) insert_mpe_episode_body<16>(e.ins, e.ins_obs_st, e.ins_rew_st, e.ins_done_st, e.T, gw - e.wI0, e.wAll - e.wI0);
 }
+#include "mlp_ep16l.h"             // the same episode with the weights in LDS (rollout_episode_lds_kernel: wA = the actor's workgroups)
 
 // trunk features of a recurrent network (mappo_mlp_features, in_dim <= 64) on the same register-resident 16x16x4 path
 template <bool RELU, int LN>
@@ -2094,6 +2095,31 @@ static int episode_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s
   return MAPPO_OK;
 }
 
+// The LDS body (mlp_ep16l.h), layer_N 0 / 1: one workgroup of EPISODE_LDS_WAVES waves per CU, each serving one network from an LDS
+// image of its weights; the workgroups are split between actor and critic by item cost per SIMD.  It is the default where the
+// register body above would run, unless one of that body's geometry overrides is set (they keep their meaning and their kernel);
+// MAPPO_EPISODE_LDS=0 / 1 forces the choice.  Overrides of its own: MAPPO_EPISODE_LDS_WAVES (waves per workgroup, 1 .. 16) and
+// MAPPO_EPISODE_LDS_ACTOR_WGS (the actor's workgroups, 1 .. workgroups - 1; 0: by cost).  Measured: DESIGN.md, round 8.
+#define EPISODE_LDS_DEFAULT 1
+#define EPISODE_LDS_WAVES 16
+#define EPISODE_LDS_COST_A 150                             // per-item costs, as for the register body (134 of 256 workgroups for the actor at the
+#define EPISODE_LDS_COST_C 134                             // bench shape; the sweep in DESIGN.md, round 8: 120 .. 130 are ~1 us shorter, 2 % of the launch)
+template <bool R, int L>
+static int episode_lds_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const EpisodeArgs &a) {
+  static const hipError_t attr_rc = hipFuncSetAttribute((const void *)rollout_episode_lds_kernel<R, L>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                        (int)(sizeof(float) * (EplMap<L>::total + EPL_MAX_WAVES * 16 * TP)));
+  if (attr_rc != hipSuccess) { mappo_set_error("rollout_episode: hipFuncSetAttribute: %s", hipGetErrorString(attr_rc)); (void)hipGetLastError(); return MAPPO_ELAUNCH; }
+  hipLaunchKernelGGL((rollout_episode_lds_kernel<R, L>), grid, block, lds_bytes, st, a);
+  return MAPPO_OK;
+}
+// which body a launch with this layer_N takes under the current environment (1: LDS, 0: registers)
+extern "C" int mappo_rollout_episode_uses_lds(int32_t layer_N) {
+  if (layer_N < 0 || layer_N > 1) return 0;
+  if (const char *ev = getenv("MAPPO_EPISODE_LDS")) return atoi(ev) != 0;
+  if (getenv("MAPPO_EPISODE_WAVES") || getenv("MAPPO_EPISODE_NET_WAVES") || getenv("MAPPO_EPISODE_INS_WAVES") || getenv("MAPPO_EPISODE_COST_A")) return 0;
+  return EPISODE_LDS_DEFAULT;
+}
+
 extern "C" int mappo_rollout_episode(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
                                      const mappo_net_desc *critic_desc, int32_t T, int32_t N, int32_t M, const float *env_obs,
                                      int64_t obs_stride_t, int64_t obs_stride_n, int64_t obs_stride_m, const float *rewards,
@@ -2123,6 +2149,7 @@ extern "C" int mappo_rollout_episode(const float *actor_params, const mappo_net_
   MAPPO_CLEAR_STICKY();
   const int64_t B = (int64_t)N * M, S = critic_desc->in_dim;
   const int64_t n_tiles = (B + 15) / 16;
+  const bool use_lds = mappo_rollout_episode_uses_lds(actor_desc->layer_N) != 0;
   int nw = env_int("MAPPO_EPISODE_WAVES", EPISODE_WAVES, 1, 4);
   if (nw != 1 && nw != 2) nw = 4;
   const int n_ins = env_int("MAPPO_EPISODE_INS_WAVES", 0, 0, 4 * NUM_CU - 2);
@@ -2154,10 +2181,34 @@ extern "C" int mappo_rollout_episode(const float *actor_params, const mappo_net_
   e.T = T; e.M = M; e.wA = (int)wa; e.wC = (int)wc;
   e.wI0 = n_ins > 0 ? e.wA + e.wC : 0;
   e.wAll = e.wA + e.wC + n_ins;
-  const dim3 grid((unsigned)((e.wAll + nw - 1) / nw)), block(WAVE * nw);
-  const size_t lds_bytes = sizeof(float) * 16 * TP * nw;   // the actor's [16][TP] logits tile per wave
   const bool relu = actor_desc->use_relu != 0;
   int rc;
+  if (use_lds) {
+    const int W = env_int("MAPPO_EPISODE_LDS_WAVES", EPISODE_LDS_WAVES, 1, EPL_MAX_WAVES);
+    // no more workgroups than have an item for every wave (at least one per network), at most one per CU
+    int64_t G = (items_a + W - 1) / W + (items_c + W - 1) / W;
+    G = G > NUM_CU ? NUM_CU : G;
+    // the actor's share: the shortest longest SIMD (a workgroup's waves sit on min(W, 4) SIMDs; items per SIMD x item cost)
+    const int simds = W < 4 ? W : 4;
+    int64_t ga = 1, lbest = -1;
+    for (int64_t a = 1; a < G; ++a) {
+      const int64_t la = (items_a + a * simds - 1) / (a * simds) * EPISODE_LDS_COST_A, lc = (items_c + (G - a) * simds - 1) / ((G - a) * simds) * EPISODE_LDS_COST_C;
+      const int64_t l = la > lc ? la : lc;
+      if (lbest < 0 || l < lbest) { lbest = l; ga = a; }
+    }
+    ga = env_int("MAPPO_EPISODE_LDS_ACTOR_WGS", 0, 0, (int)G - 1) > 0 ? env_int("MAPPO_EPISODE_LDS_ACTOR_WGS", 0, 0, (int)G - 1) : ga;
+    e.wA = (int)ga; e.wC = (int)(G - ga); e.wI0 = 0; e.wAll = (int)G * W;
+    const dim3 lgrid((unsigned)G), lblock(WAVE * W);
+    const int img = actor_desc->layer_N == 0 ? EplMap<0>::total : EplMap<1>::total;
+    const size_t lbytes = sizeof(float) * (img + W * 16 * TP);      // the network image + a [16][TP] logits tile per wave
+    if (actor_desc->layer_N == 0) rc = relu ? episode_lds_launch<true, 0>(lgrid, lblock, lbytes, as_stream(stream), e) : episode_lds_launch<false, 0>(lgrid, lblock, lbytes, as_stream(stream), e);
+    else rc = relu ? episode_lds_launch<true, 1>(lgrid, lblock, lbytes, as_stream(stream), e) : episode_lds_launch<false, 1>(lgrid, lblock, lbytes, as_stream(stream), e);
+    if (rc) return rc;
+    MAPPO_CHECK_LAUNCH("rollout_episode");
+    return MAPPO_OK;
+  }
+  const dim3 grid((unsigned)((e.wAll + nw - 1) / nw)), block(WAVE * nw);
+  const size_t lds_bytes = sizeof(float) * 16 * TP * nw;   // the actor's [16][TP] logits tile per wave
   switch (actor_desc->layer_N) {
     case 0: rc = relu ? episode_launch<true, 0>(grid, block, lds_bytes, as_stream(stream), e) : episode_launch<false, 0>(grid, block, lds_bytes, as_stream(stream), e); break;
     case 1: rc = relu ? episode_launch<true, 1>(grid, block, lds_bytes, as_stream(stream), e) : episode_launch<false, 1>(grid, block, lds_bytes, as_stream(stream), e); break;

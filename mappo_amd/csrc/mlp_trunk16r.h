@@ -73,6 +73,18 @@ struct Trunk16R {
   f32x4 g0[4], t0[4];                                            // feature-norm affine of the inputs (zero beyond in_dim)
   f32x4 b1v[4], g1[4], t1[4];
   f32x4 w2[LN > 0 ? LN : 1][4][4], b2v[LN > 0 ? LN : 1][4], g2[LN > 0 ? LN : 1][4], t2[LN > 0 ? LN : 1][4];
+  // trunk16r_apply reads its weights through these accessors only, so that a trunk whose weights live elsewhere (Trunk16L in
+  // mlp_ep16l.h: LDS) runs the same arithmetic on the same operands
+  __device__ __forceinline__ f32x4 W1(int bo, int b) const { return w1[bo][b]; }
+  __device__ __forceinline__ f32x4 G0(int b) const { return g0[b]; }
+  __device__ __forceinline__ f32x4 T0(int b) const { return t0[b]; }
+  __device__ __forceinline__ f32x4 B1(int b) const { return b1v[b]; }
+  __device__ __forceinline__ f32x4 G1(int b) const { return g1[b]; }
+  __device__ __forceinline__ f32x4 T1(int b) const { return t1[b]; }
+  __device__ __forceinline__ f32x4 W2(int l, int bo, int b) const { return w2[l][bo][b]; }
+  __device__ __forceinline__ f32x4 B2(int l, int b) const { return b2v[l][b]; }
+  __device__ __forceinline__ f32x4 G2(int l, int b) const { return g2[l][b]; }
+  __device__ __forceinline__ f32x4 T2(int l, int b) const { return t2[l][b]; }
 };
 
 // all loads of the trunk's weights and vectors for lane (j, q) (nothing waits here)
@@ -110,9 +122,10 @@ __device__ __forceinline__ void trunk16r_load(Trunk16R<LN> &w, const float *P, c
 }
 
 // x: the lane's raw inputs (feature 16 b + 4 q + r of its sample; any value beyond in_dim / for a missing sample) -> h: the
-// trunk's output (LayerNorm of the last hidden layer, affine included)
-template <bool RELU, int LN>
-__device__ __forceinline__ void trunk16r_apply(const Trunk16R<LN> &w, f32x4 (&x)[4], f32x4 (&h)[4], int D, bool ok, bool fnorm, int q) {
+// trunk's output (LayerNorm of the last hidden layer, affine included).  TW: where the weights come from (Trunk16R: registers,
+// Trunk16L: LDS) — each 16-byte operand is fetched once, where it is first used.
+template <bool RELU, int LN, class TW>
+__device__ __forceinline__ void trunk16r_apply(const TW &w, f32x4 (&x)[4], f32x4 (&h)[4], int D, bool ok, bool fnorm, int q) {
   const int NB1 = (D + 15) >> 4;
   const float inv_D = 1.0f / (float)D;
 #pragma unroll
@@ -131,33 +144,52 @@ __device__ __forceinline__ void trunk16r_apply(const Trunk16R<LN> &w, f32x4 (&x)
       for (int r = 0; r < 4; ++r) { const float c = (16 * b + 4 * q + r < D) ? x[b][r] - mean : 0.f; x[b][r] = c; v += c * c; }
     const float rstd = 1.0f / sqrtf(quad_sum16(v) * inv_D + LN_EPS);
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < 4; ++b) {
+      const f32x4 g0 = w.G0(b), t0 = w.T0(b);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) x[b][r] = (16 * b + 4 * q + r < D) ? x[b][r] * rstd * w.g0[b][r] + w.t0[b][r] : 0.f;
+      for (int r = 0; r < 4; ++r) x[b][r] = (16 * b + 4 * q + r < D) ? x[b][r] * rstd * g0[r] + t0[r] : 0.f;
+    }
   }
 #pragma unroll
-  for (int bo = 0; bo < 4; ++bo) h[bo] = w.b1v[bo];
+  for (int bo = 0; bo < 4; ++bo) h[bo] = w.B1(bo);
 #pragma unroll
   for (int b = 0; b < 4; ++b)
     if (b < NB1) {
+      f32x4 a[4];
+#pragma unroll
+      for (int bo = 0; bo < 4; ++bo) a[bo] = w.W1(bo, b);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int bo = 0; bo < 4; ++bo) h[bo] = mfma16(w.w1[bo][b][r], x[b][r], h[bo]);
+        for (int bo = 0; bo < 4; ++bo) h[bo] = mfma16(a[bo][r], x[b][r], h[bo]);
     }
-  act_ln16r<RELU>(h, w.g1, w.t1);
+  {
+    f32x4 g[4], t[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { g[b] = w.G1(b); t[b] = w.T1(b); }
+    act_ln16r<RELU>(h, g, t);
+  }
 #pragma unroll
   for (int l = 0; l < LN; ++l) {
     f32x4 h2[4];
 #pragma unroll
-    for (int bo = 0; bo < 4; ++bo) h2[bo] = w.b2v[l][bo];
+    for (int bo = 0; bo < 4; ++bo) h2[bo] = w.B2(l, bo);
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
+    for (int b = 0; b < 4; ++b) {
+      f32x4 a[4];
+#pragma unroll
+      for (int bo = 0; bo < 4; ++bo) a[bo] = w.W2(l, bo, b);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int bo = 0; bo < 4; ++bo) h2[bo] = mfma16(w.w2[l][bo][b][r], h[b][r], h2[bo]);
-    act_ln16r<RELU>(h2, w.g2[l], w.t2[l]);
+        for (int bo = 0; bo < 4; ++bo) h2[bo] = mfma16(a[bo][r], h[b][r], h2[bo]);
+    }
+    {
+      f32x4 g[4], t[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) { g[b] = w.G2(l, b); t[b] = w.T2(l, b); }
+      act_ln16r<RELU>(h2, g, t);
+    }
 #pragma unroll
     for (int b = 0; b < 4; ++b) h[b] = h2[b];
   }
