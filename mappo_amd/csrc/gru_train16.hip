@@ -24,8 +24,9 @@
 // stride 68 puts lanes (11, q) and (12, q - 1) of a group on the same bank quad: one conflict cycle in five).  Scratch is
 // BLOCKED the same way: [component][t][tile][b][lane][4] — a wave instruction moves one contiguous KiB.
 #include <stdlib.h>
-#define MLP_TU_GRU16
-#include "mlp_impl.h"
+#include "mlp_fwd.h"             // FwdArgs, act_ln16 (mlp_fwd16.h)
+#include "mlp_upd16.h"           // the 16-sample-tile helpers: ld4 / st4, quad_*16, RS16, actor-loss pieces (with mlp_trunk16r.h, mlp_blocks.h)
+#include "mlp_launch.h"          // NUM_CU
 
 #define G16_THREADS 512
 #define G16_WAVES (G16_THREADS / WAVE)

@@ -17,9 +17,12 @@
 //     stride 68: the transposed reads of lanes (n, q) hit 32 distinct banks) and reads them back k <-> sample.
 //   * bias gradients are column sums of the dz tile (lane = feature, 16 reads), so they cost one register per layer.
 // The accumulators of a wave are the RAW products of the whole network (critic, in_dim 54: 64 + 64 registers); the
-// LayerNorm-affine transform (see raw_to_grad in mlp_impl.h) is linear in them and is applied ONCE per workgroup, after
+// LayerNorm-affine transform (see raw_to_grad in mlp_blocks.h) is linear in them and is applied ONCE per workgroup, after
 // the waves' accumulators have been summed in LDS, by all threads.
 #pragma once
+#include "mlp_upd_args.h"
+#include "mlp_stamps.h"
+#include "mlp_trunk16r.h"
 #include <utility>
 #include <type_traits>
 
@@ -61,7 +64,7 @@ struct L16 {
   static constexpr int DMAX = XL1 ? 0 : (WIDE ? 64 : 32);
   static constexpr int PMAX = 2 * DMAX + HID * DMAX + 3 * HID + (LN > 0 ? HID * HID + 3 * HID : 0) + (HEAD == 1 ? 16 * HID + 16 : HID + 1);
   // 8 accumulators per reduction chunk (half the rounds, each with two barriers) where the LDS allows it: the tile area
-  // grows to the chunk buffer's need when that still fits UPD16_LDS_MAX (mlp_impl.h) and the layout already holds more
+  // grows to the chunk buffer's need when that still fits UPD16_LDS_MAX (mlp_launch.h) and the layout already holds more
   // than half of it (one workgroup per CU either way); 4 otherwise
   static constexpr int LDS_CAP = (160 * 1024 - 256) / 4;
   static constexpr int EPI4 = 1024 + N_WAVES * 4 * 256 + PMAX, EPI8 = 1024 + N_WAVES * 8 * 256 + PMAX;
@@ -393,7 +396,7 @@ __device__ __forceinline__ float critic_loss16(float v, float vo, float ret, flo
   return dv;
 }
 
-// Epilogue transform of one weight matrix with a LayerNorm affine on its input (raw_to_grad, mlp_impl.h), on the
+// Epilogue transform of one weight matrix with a LayerNorm affine on its input (raw_to_grad, mlp_blocks.h), on the
 // workgroup's summed raw products in R:  G at R[wo + f K + k], db at R[bo + f] (f < F <= 8 NJ, k < K <= 64).
 //   R[wo..] <- gam[k] G + bet[k] db[f];  R[go + k] <- sum_f W[f][k] G[f][k];  R[to + k] <- sum_f W[f][k] db[f]
 // Thread (k = tid & 63, part = tid >> 6) owns rows f = part + 8 j; w[j] = W[f][k] (raw, preloaded from global memory).

@@ -1,9 +1,9 @@
 // mlp_upd2.h — the update kernel for in_dim <= 64 ("pair" formulation): forward + head gradient (external | PPO actor
-// loss | value loss | trunk gradient in) + backward, like mlp_update_kernel (mlp_impl.h), but with TWO wavefronts per
+// loss | value loss | trunk gradient in) + backward, like mlp_update_kernel (mlp_upd.h), but with TWO wavefronts per
 // 32-sample tile.
 //
 // Why: with one wave per tile the 64x64 gradient accumulators need ~450 registers, which limits a CU to 4 waves (one
-// per SIMD) — and a lone wave cannot hide its own LDS / MFMA latencies (scripts/exp_waves.py: 2 waves per SIMD run the
+// per SIMD) — and a lone wave cannot hide its own LDS / MFMA latencies (an 8-wave build of the one-wave kernel: 2 waves per SIMD run the
 // per-tile work ~1.7x faster).  Here the two waves of a pair split every layer's 64 OUTPUT features 32 / 32:
 //   wave `fh` of a pair owns rows [32 fh, 32 fh + 32) of every activation, of every dz and of every weight gradient.
 // Each wave then carries half the accumulators (<= 256 registers), a workgroup holds 8 waves = 2 per SIMD, and the
@@ -14,8 +14,10 @@
 //     (11 per tile for layer_N = 1).  Pairs are not synchronised with each other inside the tile loop, so the two
 //     tiles that share a SIMD drift apart and fill each other's MFMA / VALU / LDS latencies.
 //   * the head forward + per-sample loss (32 lanes of work) is done by wave 0 of the pair while wave 1 waits.
-// Accumulated quantities are the RAW products (see raw_to_grad in mlp_impl.h); the epilogue is per wave.
+// Accumulated quantities are the RAW products (see raw_to_grad in mlp_blocks.h); the epilogue is per wave.
 #pragma once
+#include "mlp_upd_args.h"
+#include "mlp_stamps.h"
 
 #define XS 65            // row stride (floats) of the flat-commit staging area: lanes (s16, q) hit 64 distinct banks
 
@@ -346,7 +348,7 @@ __device__ __forceinline__ void raw_w_load(float (&w)[NTJ][16], const float *__r
   }
 }
 
-// raw products -> gradient partials (see raw_to_grad in mlp_impl.h).  dbv: db of row frow0 + l31 (any half).
+// raw products -> gradient partials (see raw_to_grad in mlp_blocks.h).  dbv: db of row frow0 + l31 (any half).
 // dg / dt (per tile): this wave's partial d gamma / d beta of column k, valid in every lane of that l31.
 template <int NTJ>
 __device__ __forceinline__ void raw_to_grad1(f32x16 (&g)[NTJ], const float (&w)[NTJ][16], float dbv, float *scr, const float *sG,

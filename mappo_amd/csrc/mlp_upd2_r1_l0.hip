@@ -1,5 +1,4 @@
 // mlp_update2_kernel<RELU=true, LN=0, HEAD 0..3, WIDE 0..1> — the pair update kernel (see mlp_upd2.h)
-#define MLP_TU_UPD2
 #define MLP_UPD_RELU true
 #define MLP_UPD_LN 0
-#include "mlp_impl.h"
+#include "mlp_upd2_launch.h"

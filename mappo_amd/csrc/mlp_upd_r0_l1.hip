@@ -1,5 +1,4 @@
-// mlp_update_kernel<RELU=false, LN=1, HEAD 0..3, XW 0..2> (see mlp_impl.h)
-#define MLP_TU_UPD
+// mlp_update_kernel<RELU=false, LN=1, HEAD 0..3> — the K-chunked wide update kernel (mlp_upd.h)
 #define MLP_UPD_RELU false
 #define MLP_UPD_LN 1
-#include "mlp_impl.h"
+#include "mlp_upd_launch.h"

@@ -1,5 +1,4 @@
-// mlp_update_kernel<RELU=true, LN=0, HEAD 0..3, XW 0..2> (see mlp_impl.h)
-#define MLP_TU_UPD
+// mlp_update_kernel<RELU=true, LN=0, HEAD 0..3> — the K-chunked wide update kernel (mlp_upd.h)
 #define MLP_UPD_RELU true
 #define MLP_UPD_LN 0
-#include "mlp_impl.h"
+#include "mlp_upd_launch.h"

@@ -848,55 +848,12 @@ __global__ __launch_bounds__(256, 1) void wide_features16_sk_dual_kernel(WideDua
   else wide_forward16_sk_body<RELU, LN, 2>(d.wc, d.c, lds, sh, (int)blockIdx.x - d.nA, (int)gridDim.x - d.nA);
 }
 
-#ifdef MLP_TU_WIDE_SK
-// ---- one rollout step of a recurrent actor AND critic with wide inputs in ONE launch (r_actor_critic.py:43-70,146-165;
-// smac_runner.py:110-127) ----
-// Round 2 ran such a step as two launches (mappo_mlp_features_dual: split-K trunks -> featT in HBM; mappo_gru_step_dual: GRU cell +
-// rnn.norm + heads), 21 + 14 us at BASELINE configs[3] where the arithmetic is a few microseconds: two launch latencies, two
-// weight-fetch latencies and a feature round trip through HBM.  Here the 4-wave workgroup that runs a tile's split-K trunk goes
-// straight on to the tile's GRU step: the GRU / head operands of every wave are requested BEFORE the trunk starts (they land
-// under it), wave 0's trunk output crosses to the other waves through 4 KB of LDS, and gru_step3_tiles finishes the row.
-#include "gru_step3.h"
-struct WideRecDualArgs {
-  WideDualArgs d;
-  GruFwdArgs ga, gc;
-  SmacInsert ins;             // nI > 0: workgroups [2 nA, 2 nA + nI) perform the SMAC insert of the env output the rows are read from
-  int nI;
-};
-template <bool RELU, int LN>
-__global__ __launch_bounds__(256, 1) void wide_recurrent_step_dual_kernel(WideRecDualArgs r) {
-  extern __shared__ __align__(16) float lds[];
-  __shared__ SkShared sh;
-  __shared__ Step3Shared s3;
-  __shared__ float4 sX[4 * 64];
-  const int lane = threadIdx.x & 63, n = lane & 15, q = lane >> 4;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const bool actor = (int)blockIdx.x < r.d.nA;                    // one tile per workgroup: grid = 2 x tiles (+ insert workgroups)
-  const int bid = actor ? (int)blockIdx.x : (int)blockIdx.x - r.d.nA, nb = r.d.nA;
-  if ((int)blockIdx.x >= 2 * r.d.nA) { insert_smac_body(r.ins, (int)blockIdx.x - 2 * r.d.nA, r.nI); return; }
-  Step3W<0> W;
-  // (the GRU step's 96 weight registers are requested BEHIND the trunk's own weights and rows: asked for first, they were what the
-  // trunk's first MFMA waited for)
-  if (actor) {
-    wide_forward16_sk_body<RELU, LN, 4>(r.d.wa, r.d.a, lds, sh, bid, nb, reinterpret_cast<float *>(sX),
-                                        [&]() __attribute__((always_inline)) { gru_step3_load<3, 0>(W, r.ga, wv, n, q); });
-    gru_step3_tiles<2, 3, 0>(W, r.ga, s3, bid, nb, sX);
-  } else {
-    wide_forward16_sk_body<RELU, LN, 4>(r.d.wc, r.d.c, lds, sh, bid, nb, reinterpret_cast<float *>(sX),
-                                        [&]() __attribute__((always_inline)) { gru_step3_load<3, 0>(W, r.gc, wv, n, q); });
-    gru_step3_tiles<1, 3, 0>(W, r.gc, s3, bid, nb, sX);
-  }
-}
-#undef GS
-#undef NG
-#endif
-
 // ------------------------------------------------------------------------------------------------------------------------
 // wide_l1_bwd16_kernel — weight gradient of layer 1 and the feature-norm gradients for in_dim 65..512 from dz1 and the row
 // statistics the forward left (workspace layout below):
 //     G[f][k] = sum_s dz1[f][s] xhat0[k][s]   (RAW product: xhat0 without the affine),   db[f] = sum_s dz1[f][s]
 //     dW1 = gamma0[k] G + beta0[k] db[f],   dgamma0[k] = sum_f W1[f][k] G[f][k],   dbeta0[k] = sum_f W1[f][k] db[f]
-// (the raw-product identities of mlp_impl.h: no dX = W1^T dz1 pass — half the MFMA work of the round-1 kernel, which also
+// (the raw-product identities of raw_to_grad, mlp_blocks.h: no dX = W1^T dz1 pass — half the MFMA work of the round-1 kernel, which also
 // re-read dz1 once per 64-column chunk).  A workgroup walks 16-sample tiles; wave w owns the 64-column chunk w % NCA of W1's
 // gradient (64 accumulator registers) for the tiles of its tile group w / NCA:
 //   * A operand = dz1^T: lane (m, q) needs dz1[16 bf + m][4 q .. 4 q + 3] — ONE 16-byte load; dz1 is stored BLOCKED,

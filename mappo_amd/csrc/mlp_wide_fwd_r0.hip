@@ -1,4 +1,3 @@
 // wide-input kernels (mlp_wide16.h): the streamed one-launch forward and its dual form, activation = tanh
-#define MLP_TU_WIDE_FWD
 #define MLP_WIDE_RELU false
-#include "mlp_impl.h"
+#include "mlp_wide_fwd_launch.h"

@@ -1,3 +1,3 @@
 // rollout_spread.hip — the one-launch rollout episode on the GPU-resident simple_spread environment (see rollout_spread.h)
-#define MLP_TU_SPREAD
-#include "mlp_impl.h"
+#include "mlp_host.h"
+#include "rollout_spread.h"

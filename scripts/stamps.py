@@ -7,7 +7,7 @@ ROOT = os.getcwd()
 out = os.path.join(ROOT, 'gpurun_out', 'libmappo_hip_stamps.so')
 from mappo_amd import build as _build
 objdir = os.path.join(ROOT, 'gpurun_out', 'stamps_obj'); os.makedirs(objdir, exist_ok=True)
-_build.build(force=True, verbose=False, extra_flags=['-DMLP_STAMPS', '-w'] + os.environ.get('STAMP_FLAGS', '').split(), lib=out, objdir=objdir)
+_build.build(force=True, verbose=False, extra_flags=['-DMLP_STAMPS', '-w'], lib=out, objdir=objdir)
 from mappo_amd import _lib
 _lib.LIB_PATH = out
 _lib.SIGNATURES['mappo_debug_set_stamps'] = (ctypes.c_int, [ctypes.c_void_p])

@@ -110,24 +110,24 @@ def rows_of(c):
 
 # ---- Python mirror of the host dispatch -------------------------------------------------------------------------------------------
 def act_instance(c):
-    """launch_forward<1> (csrc/mlp_impl.h:2178-2243): wide inputs split-K up to WIDE_SK_MAX_TILES = 256 16-row tiles
-    (mlp_impl.h:1392, 2200-2208) else streamed (:2220); narrow mlp_forward_kernel<RELU, LN, 1, XW>, XW by in_dim (:2233-2238)."""
+    """launch_forward<1> (csrc/mlp.hip): wide inputs split-K up to WIDE_SK_MAX_TILES = 256 16-row tiles (mlp_launch.h;
+    wide16_launch_forward_sk) else streamed (wide16_launch_forward); narrow mlp_forward_kernel<RELU, LN, 1, XW>, XW by in_dim."""
     if c.D > 64:
         return ("wide_sk" if _cdiv(c.N, 16) <= 256 else "wide_streamed",)
     return ("narrow", c.relu, c.LN, 1 if c.D > 32 else 0)
 
 
 def act_walks(c):
-    """mlp_impl.h:2180-2191: 32-row tiles, up to 4 waves per workgroup (fit_waves can only lower that), at most NUM_CU workgroups."""
+    """launch_forward (csrc/mlp.hip): 32-row tiles, up to 4 waves per workgroup (fit_waves can only lower that), at most NUM_CU workgroups."""
     n_tiles = _cdiv(c.N, 32)
     nw = 4 if n_tiles >= 4 else (2 if n_tiles >= 2 else 1)
     return n_tiles > min(_cdiv(n_tiles, nw), NUM_CU) * nw
 
 
 def step_instance(c):
-    """mappo_rollout_step (mlp_impl.h:1979-2070): wide -> wide_rollout_full_kernel for 256 / 512 on both networks and at most two
-    tiles per wave (:1984-1988, fused insert only for uncentralized rows with agent stride in_dim), else wide_rollout_step_kernel;
-    narrow -> rollout_step_kernel<RELU, LN> (:2066-2070), at most NUM_CU / 2 workgroups of <= 4 waves x 16 rows per network (:2035-2053)."""
+    """mappo_rollout_step (csrc/mlp_step.hip): wide -> wide_rollout_full_kernel for 256 / 512 on both networks and at most two
+    tiles per wave (full_step / fuse_ins: fused insert only for uncentralized rows with agent stride in_dim), else
+    wide_rollout_step_kernel; narrow -> rollout_step_kernel<RELU, LN>, at most NUM_CU / 2 workgroups of <= 4 waves x 16 rows per network."""
     B = rows_of(c)
     if c.D > 64:
         full = c.D == c.S and c.D in (256, 512) and _cdiv(B, 16) <= 2 * 8 * (NUM_CU // 2)
@@ -138,13 +138,13 @@ def step_instance(c):
 def step_tiles_per_wave(c):
     n_tiles = _cdiv(rows_of(c), 16)
     if c.D > 64:
-        return _cdiv(n_tiles, min(_cdiv(n_tiles, 8), NUM_CU // 2) * 8)            # mlp_impl.h:2007-2008
+        return _cdiv(n_tiles, min(_cdiv(n_tiles, 8), NUM_CU // 2) * 8)            # mappo_rollout_step, wide branch: n_groups / nb
     nw = 4 if n_tiles >= 4 else (2 if n_tiles >= 2 else 1)
     return _cdiv(n_tiles, min(_cdiv(n_tiles, nw), NUM_CU // 2) * nw)
 
 
 def episode_items_per_wave(c):
-    """mappo_rollout_episode (mlp_impl.h:2125-2140): (step, tile) items dealt over 4 NUM_CU waves, split by item cost 150 : 134."""
+    """mappo_rollout_episode (csrc/mlp_step.hip): (step, tile) items dealt over 4 NUM_CU waves, split by item cost 150 : 134."""
     n_tiles, n_net = _cdiv(c.N * c.M, 16), 4 * NUM_CU
     items_a, items_c = c.TT * n_tiles, (c.TT + 1) * n_tiles
     best, wa = None, 1

@@ -1,12 +1,12 @@
 """Every fused PPO update path against a float64 reference.
 
-mappo_actor_update / mappo_critic_update (launch_update<HEAD> in mlp_impl.h) and mappo_actor_critic_update choose among four
+mappo_actor_update / mappo_critic_update (launch_update<HEAD> in mlp.hip) and mappo_actor_critic_update choose among four
 kernel families, each instantiated over the activation, layer_N and (network, input width):
 
     upd16   one wave per 16-sample tile (mlp_upd16.h)          in_dim <= 64, layer_N <= 1, actor out_dim <= 16, LDS layout fits
     upd16x  the same from z1 on, layer 1 in mlp_wide16.h      65..512 inputs, layer_N <= 1, actor out_dim <= 16
     upd2    pair kernel (mlp_upd2.h)                           in_dim <= 64 otherwise
-    wide    K-chunked wide kernel (mlp_update_kernel, XW = 2)  65..512 inputs otherwise
+    wide    K-chunked wide kernel (mlp_update_kernel, mlp_upd.h)  65..512 inputs otherwise
 
 and the dual launch takes upd16d (both networks upd16) or upd2d (the pair kernel for both).  MATRIX is a covering design of
 those instances with every loss flag set and feature normalisation off on every family; test_matrix_covers_every_instance
@@ -28,7 +28,7 @@ from oracle import mappo_oracle as O
 from test_gpu_e2e import M, make_args, set_vn, TUPLE   # noqa: F401  (M: the trainer-level fixture)
 from test_gpu_kernels import close, close_rel_max, dev, _flat_from_module, _randomize, _relu_margin, _loss_margin
 
-# ---- Python mirror of the dispatch (mappo_amd/csrc/mlp_impl.h, mlp_upd16.h) -------------------------------------------
+# ---- Python mirror of the dispatch (mappo_amd/csrc/mlp.hip, mlp_upd16.h) -------------------------------------------
 HID, NUM_CU, UPD16_WAVES, TS = 64, 256, 8, 32
 UPD16_LDS_MAX = 160 * 1024 - 256                                     # UPD16_LDS_MAX
 
