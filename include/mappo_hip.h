@@ -200,6 +200,28 @@ int mappo_rollout_step(const float *actor_params, const mappo_net_desc *actor_de
                        float *values /*[B]*/, float *obs_dst /*or NULL: no insert*/, float *share_dst, const float *rewards,
                        int64_t rew_stride_n, int64_t rew_stride_m, const uint8_t *dones, int64_t done_stride_n,
                        int64_t done_stride_m, float *rew_dst, float *mask_dst, int32_t centralized, mappo_stream_t stream);
+/* ---- MultiDiscrete action spaces (envs/mpe/environment.py:82-86; act.py:27-33,65-76,139-152): one Categorical head per
+ * sub-action.  Head j has d_j = head_dims[j] actions; the actor's out_dim is A = sum d_j and its head parameters are the heads'
+ * weight rows / biases side by side (W[A][H] | b[A], head j = rows [d_0 + .. + d_{j-1}, .. + d_j)).  actions / logp are [B][K]
+ * (K = n_heads): the head-local index as fp32 and one log-prob per head, not summed.
+ * Limits, checked on the host before any launch (MAPPO_EINVAL, mappo_last_error() names the limit): 1 <= K <= 4, every d_j >= 1,
+ * sum d_j == out_dim <= 16, in_dim <= 64, layer_N <= 1, not recurrent, avail == NULL (the space has no available_actions).
+ * Sampling contract: head j of row i draws Philox index (j << 32) | i — counter words {i, j, counter lo, counter hi} — with the key
+ * and counter of the contract above; inside a head the rule is the same (first a with u < C_a, fallback to the last action with
+ * p > 0, deterministic = first maximum).  Head 0 therefore draws exactly what a Discrete policy draws. */
+int mappo_actor_act_md(const float *params, const mappo_net_desc *desc /*host*/, const float *obs, const float *avail /*NULL*/,
+                       const int32_t *head_dims /*host*/, int32_t n_heads, int64_t B, int32_t deterministic, uint64_t seed,
+                       uint64_t counter, const uint64_t *counter_dev, float *actions /*[B][K]*/, float *logp /*[B][K]*/,
+                       mappo_stream_t stream);
+/* mappo_rollout_step for such a policy: actor + critic + optional insert in one launch (both networks in_dim <= 64). */
+int mappo_rollout_step_md(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *critic_params,
+                          const mappo_net_desc *critic_desc /*host*/, const float *obs, int64_t obs_stride_n, int64_t obs_stride_m,
+                          const float *share_obs, int64_t share_stride_n, int64_t share_stride_m, int32_t M, int64_t B,
+                          const float *avail /*NULL*/, const int32_t *head_dims /*host*/, int32_t n_heads, int32_t deterministic,
+                          uint64_t seed, uint64_t counter, const uint64_t *counter_dev, float *actions /*[B][K]*/, float *logp /*[B][K]*/,
+                          float *values /*[B]*/, float *obs_dst /*or NULL: no insert*/, float *share_dst, const float *rewards,
+                          int64_t rew_stride_n, int64_t rew_stride_m, const uint8_t *dones, int64_t done_stride_n, int64_t done_stride_m,
+                          float *rew_dst, float *mask_dst, int32_t centralized, mappo_stream_t stream);
 /* One launch per rollout EPISODE, for envs whose output for the whole episode exists before it starts and does not depend on
  * the actions (synthetic MPE): what T + 1 mappo_rollout_step calls do, with the env output of step t at
  * env_obs[t*obs_stride_t + n*obs_stride_n + m*obs_stride_m + d], rewards / dones likewise (bool bytes).  Actor on the rows of
@@ -281,6 +303,23 @@ int mappo_actor_critic_update(const float *actor_params, const mappo_net_desc *a
                               const float *vn_state, const double *mb_moments, const mappo_ppo_cfg *cfg /*host*/, float *slabs,
                               int64_t slab_stride, int64_t actor_col0, int64_t critic_col0, double *actor_partials,
                               double *critic_partials, mappo_stream_t stream);
+/* The same two launches for a MultiDiscrete actor (limits and layout: mappo_actor_act_md; r_mappo.py:124-141 with act.py:139-152):
+ * actions / old_logp are [.][K] in buffer order.  With r_j = exp(lp_j - old_lp_j) and s_j = min(r_j adv, clip(r_j) adv) the actor's
+ * per-workgroup partials are {sum w sum_j s_j, sum w (1/K) sum_j H_j, sum (1/K) sum_j r_j, -}, so mappo_update_stats yields the policy
+ * loss, the mean-of-heads entropy and the mean ratio over all B K entries unchanged.  Slab / partial rows: as for the Discrete
+ * launches (mappo_mlp_backward_slabs / n_blocks; mappo_dual_update_slabs PER NETWORK, every one of them written). */
+int mappo_actor_update_md(const float *params, const mappo_net_desc *desc /*host*/, const float *obs, const int32_t *rows, int64_t B,
+                          const float *avail /*NULL*/, const int32_t *head_dims /*host*/, int32_t n_heads, const float *actions /*[.][K]*/,
+                          const float *old_logp /*[.][K]*/, const float *adv, const float *active, const double *mb_moments /*[4]*/,
+                          const mappo_ppo_cfg *cfg /*host*/, float *slabs, int64_t slab_stride, int64_t slab_col0, double *partials,
+                          float *wide_ws /*unused (in_dim <= 64): NULL*/, int32_t n_blocks, mappo_stream_t stream);
+int mappo_actor_critic_update_md(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *obs,
+                                 const float *critic_params, const mappo_net_desc *critic_desc /*host*/, const float *share_obs,
+                                 const int32_t *rows, int64_t B, const float *avail /*NULL*/, const int32_t *head_dims /*host*/,
+                                 int32_t n_heads, const float *actions, const float *old_logp, const float *adv, const float *active,
+                                 const float *v_old, const float *returns, const float *vn_state, const double *mb_moments,
+                                 const mappo_ppo_cfg *cfg /*host*/, float *slabs, int64_t slab_stride, int64_t actor_col0,
+                                 int64_t critic_col0, double *actor_partials, double *critic_partials, mappo_stream_t stream);
 int mappo_update_stats(const double *actor_partials, int32_t n_actor /*workgroups that wrote them*/,
                        const double *critic_partials, int32_t n_critic, const double *mb_moments,
                        const mappo_ppo_cfg *cfg /*host*/, double *stats /*[6]*/,

@@ -59,6 +59,10 @@ SIGNATURES = {
     "mappo_actor_act": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _I64, _I32, _U64, _U64, _P, _P, _P, _P]),
     "mappo_rollout_step": (C.c_int, [_P, C.POINTER(NetDesc), _P, C.POINTER(NetDesc), _P, _I64, _I64, _P, _I64, _I64, _I32, _I64, _P, _I32,
                                      _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I32, _P]),
+    "mappo_actor_act_md": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, C.POINTER(_I32), _I32, _I64, _I32, _U64, _U64, _P, _P, _P, _P]),
+    "mappo_rollout_step_md": (C.c_int, [_P, C.POINTER(NetDesc), _P, C.POINTER(NetDesc), _P, _I64, _I64, _P, _I64, _I64, _I32, _I64, _P,
+                                        C.POINTER(_I32), _I32, _I32, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P,
+                                        _I32, _P]),
     "mappo_rollout_episode": (C.c_int, [_P, C.POINTER(NetDesc), _P, C.POINTER(NetDesc), _I32, _I32, _I32, _P, _I64, _I64, _I64, _P, _I64,
                                         _I64, _I64, _P, _I64, _I64, _I64, _I32, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
     "mappo_rollout_episode_uses_lds": (C.c_int, [_I32]),
@@ -76,6 +80,10 @@ SIGNATURES = {
     "mappo_dual_update_slabs": (_I32, [C.POINTER(NetDesc), C.POINTER(NetDesc), _I64]),
     "mappo_actor_critic_update": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, C.POINTER(NetDesc), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                             C.POINTER(PpoCfg), _P, _I64, _I64, _I64, _P, _P, _P]),
+    "mappo_actor_update_md": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _I64, _P, C.POINTER(_I32), _I32, _P, _P, _P, _P, _P, C.POINTER(PpoCfg),
+                                        _P, _I64, _I64, _P, _P, _I32, _P]),
+    "mappo_actor_critic_update_md": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, C.POINTER(NetDesc), _P, _P, _I64, _P, C.POINTER(_I32), _I32,
+                                               _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(PpoCfg), _P, _I64, _I64, _I64, _P, _P, _P]),
     "mappo_update_stats": (C.c_int, [_P, _I32, _P, _I32, _P, C.POINTER(PpoCfg), _P, _P, _P]),
     "mappo_mlp_features": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _I64, _P, _P]),
     "mappo_gru_forward": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _U64, _U64,

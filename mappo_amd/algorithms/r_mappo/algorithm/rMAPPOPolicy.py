@@ -71,9 +71,11 @@ class R_MAPPOPolicy:
         self.act_space = act_space
 
         # sizes first (descriptors only), then one allocation for both networks
-        from mappo_amd.utils.util import obs_dim_of
+        from mappo_amd.utils.util import head_dims_of, obs_dim_of
         rec = bool(args.use_recurrent_policy or args.use_naive_recurrent_policy)
-        da = ops.net_desc(obs_dim_of(obs_space), act_space.n, args.layer_N, args.use_ReLU, args.use_feature_normalization,
+        if act_space.__class__.__name__ not in ("Discrete", "MultiDiscrete"):
+            raise NotImplementedError(f"{act_space.__class__.__name__} action space (this build covers Discrete and MultiDiscrete)")
+        da = ops.net_desc(obs_dim_of(obs_space), sum(head_dims_of(act_space)), args.layer_N, args.use_ReLU, args.use_feature_normalization,
                           rec, args.hidden_size)
         dc = ops.net_desc(obs_dim_of(cent_obs_space), 1, args.layer_N, args.use_ReLU, args.use_feature_normalization,
                           rec, args.hidden_size)
@@ -182,6 +184,13 @@ class R_MAPPOPolicy:
             insert = dict(obs_dst=buffer.obs[step], share_dst=buffer.share_obs[step], rewards=(rewards, rewards.stride(0), rewards.stride(1)),
                           dones=(dones, dones.stride(0), dones.stride(1)), rew_dst=buffer.rewards[step - 1], mask_dst=buffer.masks[step],
                           centralized=centralized)
+        hd = self.actor.head_dims
+        if hd and values_only is None:
+            # MultiDiscrete: the same launch with one sample per head, K-wide action / log-prob slots
+            ops.rollout_step_md(self.actor.flat, self.actor.desc, self.critic.flat, self.critic.desc, obs_src, share_src, Mk, R, hd,
+                                deterministic, self.actor._seed, step, self.actor._counter_dev, buffer.actions[step].view(R, len(hd)),
+                                buffer.action_log_probs[step].view(R, len(hd)), buffer.value_preds[step].view(R), insert)
+            return buffer.actions[step]
         if values_only is not None:
             ops.rollout_step(self.actor.flat, self.actor.desc, self.critic.flat, self.critic.desc, obs_src, share_src, Mk, R, None,
                              deterministic, self.actor._seed, step, None, None, None, values_only, insert)
@@ -192,8 +201,9 @@ class R_MAPPOPolicy:
         return buffer.actions[step]
 
     def can_fuse_episode(self):
-        """mappo_rollout_episode covers the narrow networks of the stepwise kernel (in_dim <= 64), not recurrent."""
-        return self.can_fuse_step() and max(self.actor.desc.in_dim, self.critic.desc.in_dim) <= 64
+        """mappo_rollout_episode covers the narrow networks of the stepwise kernel (in_dim <= 64), not recurrent, with one
+        Categorical head: a MultiDiscrete policy takes the stepwise path."""
+        return self.can_fuse_step() and max(self.actor.desc.in_dim, self.critic.desc.in_dim) <= 64 and not self.actor.head_dims
 
     @torch.no_grad()
     def collect_episode_fused(self, buffer, block, next_values, centralized=True, deterministic=False):
@@ -292,7 +302,9 @@ class R_MAPPOPolicy:
         next rnn states (recurrent policies) go to slot step+1.  Returns the fp32 actions view [N, M, 1]."""
         R = buffer.n_rollout_threads * buffer.num_agents
         avail = buffer.available_actions[step].view(R, -1) if use_available_actions else None
-        out = (buffer.actions[step].view(R), buffer.action_log_probs[step].view(R))
+        hd = self.actor.head_dims
+        out = (buffer.actions[step].view(R, len(hd)), buffer.action_log_probs[step].view(R, len(hd))) if hd else \
+            (buffer.actions[step].view(R), buffer.action_log_probs[step].view(R))
         masks = buffer.masks[step].view(R, 1)
         if getattr(self.actor, "_recurrent", False) and getattr(self.critic, "_recurrent", False):
             from mappo_amd import recurrent

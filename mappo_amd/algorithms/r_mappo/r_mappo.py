@@ -68,6 +68,14 @@ class R_MAPPO():
         self._dual_update = bool(getattr(args, "dual_update", True)) and os.environ.get("MAPPO_DUAL_UPDATE", "1") != "0"
         self._epochs = None                        # whole-buffer fused train(): per-epoch ValueNorm states + deferred statistics
         self._dist = dist_group                      # mappo_amd.distributed.DataParallel or None
+        if getattr(policy.actor, "head_dims", None):
+            # MultiDiscrete: only the single-process fused update is built (the checks come before anything is touched)
+            if dist_group is not None:
+                raise NotImplementedError("MultiDiscrete action space under the data-parallel trainer: the multi-head update is built for "
+                                          "single-process training only")
+            if not self._fused:
+                raise NotImplementedError("unfused_update with a MultiDiscrete action space: the loss of several heads exists in the fused "
+                                          "update kernels only")
         if dist_group is not None:
             # the actor keyed its sampling stream by the rank it saw at construction — rank 0 if the process group was created
             # AFTER the policy; re-key from the group this trainer reduces over, so shards never share exploration noise
@@ -158,6 +166,7 @@ class R_MAPPO():
                 vn_state = ep["states"][ep["e"]]              # state after this epoch's ValueNorm.update
         elif self._use_valuenorm:
             ops.valuenorm_update(vn_state, self._mb_moments, self.value_normalizer.beta)
+        hd = pol.actor.head_dims                             # MultiDiscrete: the multi-head update kernels (mappo_*_md; see __init__)
         slabs = self._buf("slabs", (n_slabs, P), zero=True)
         if not update_actor and not self._actor_slabs_clean:
             slabs[:, :pol.seg_bounds[1]].zero_()
@@ -168,7 +177,7 @@ class R_MAPPO():
             # the other.  --concurrent_update instead splits the 256 CUs between the two networks and launches them on two
             # streams; on MI355X this measured SLOWER (train 3.08 ms vs 2.52 ms at config 2), so it is off by default.
             na, nc = (0, 0)
-            if update_actor and self._concurrent_update:      # measured slower on MI355X (the kernels interfere): off by default
+            if update_actor and self._concurrent_update and not hd:      # measured slower on MI355X (the kernels interfere): off by default
                 na, nc = self._split_grid(n_slabs, pol.actor.desc.in_dim, pol.critic.desc.in_dim, B)
             if na:
                 cur = torch.cuda.current_stream()
@@ -183,6 +192,12 @@ class R_MAPPO():
                                   src["active"], vn_state, self._mb_moments, cfg, slabs, P, pol.seg_bounds[1], pc, nc)
                 cur.wait_stream(side)
                 n_pa, n_pc = na, nc
+            elif hd and update_actor and self._dual_update and pol.can_dual_update():
+                ops.actor_critic_update_md(pol.actor.flat, pol.actor.desc, src["obs"], pol.critic.flat, pol.critic.desc, src["share_obs"],
+                                           rows, B, hd, src["actions"], src["old_logp"], src["adv"], src["active"], src["v_old"],
+                                           src["returns"], vn_state, self._mb_moments, cfg, slabs, P, 0, pol.seg_bounds[1], pa, pc)
+                n_pa = n_pc = ops.dual_update_slabs(pol.actor.desc, pol.critic.desc, B)
+                self._slab_rows = n_pa
             elif update_actor and self._dual_update and pol.can_dual_update():
                 # both networks in ONE launch, half the CUs each (mappo_actor_critic_update): one ragged tail instead of two
                 ops.actor_critic_update(pol.actor.flat, pol.actor.desc, src["obs"], pol.critic.flat, pol.critic.desc, src["share_obs"],
@@ -191,7 +206,10 @@ class R_MAPPO():
                 n_pa = n_pc = ops.dual_update_slabs(pol.actor.desc, pol.critic.desc, B)
                 self._slab_rows = n_pa
             else:
-                if update_actor:
+                if update_actor and hd:
+                    ops.actor_update_md(pol.actor.flat, pol.actor.desc, src["obs"], rows, B, hd, src["actions"], src["old_logp"],
+                                        src["adv"], src["active"], self._mb_moments, cfg, slabs, P, 0, pa)
+                elif update_actor:
                     ops.actor_update(pol.actor.flat, pol.actor.desc, src["obs"], rows, B, src["avail"], src["actions"],
                                      src["old_logp"], src["adv"], src["active"], self._mb_moments, cfg, slabs, P, 0, pa)
                 ops.critic_update(pol.critic.flat, pol.critic.desc, src["share_obs"], rows, B, src["v_old"], src["returns"],
@@ -244,7 +262,7 @@ class R_MAPPO():
         flat = lambda a: a[:T].view(S, -1)
         return dict(obs=flat(buffer.obs), share_obs=flat(buffer.share_obs),
                     avail=flat(buffer.available_actions) if buffer.available_actions is not None else None,
-                    actions=buffer.actions.view(S), old_logp=buffer.action_log_probs.view(S), adv=adv,
+                    actions=buffer.actions.view(S, -1).squeeze(-1), old_logp=buffer.action_log_probs.view(S, -1).squeeze(-1), adv=adv,
                     active=buffer.active_masks[:T].view(S), v_old=buffer.value_preds[:T].view(S),
                     returns=buffer.returns[:T].view(S)), S
 
@@ -403,7 +421,8 @@ class R_MAPPO():
         d = lambda x: to_device_f32(x, self.device)
         B = np.shape(obs)[0] if not torch.is_tensor(obs) else obs.shape[0]
         src = dict(obs=d(obs), share_obs=d(share_obs), avail=d(avail) if avail is not None else None,
-                   actions=d(actions).view(B), old_logp=d(old_logp).view(B), adv=d(adv).view(B), active=d(active).view(B),
+                   actions=d(actions).view(B, -1).squeeze(-1), old_logp=d(old_logp).view(B, -1).squeeze(-1), adv=d(adv).view(B),
+                   active=d(active).view(B),
                    v_old=d(v_old).view(B), returns=d(ret).view(B))
         self._acc.zero_()
         self._update(src, None, B, update_actor)

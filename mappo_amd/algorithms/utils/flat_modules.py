@@ -50,7 +50,7 @@ def owned_linear_ln_block(in_dim, hidden, device):
 
 
 @torch.no_grad()
-def reference_init_state(args, in_dim, out_dim, head_prefix, head_gain, recurrent):
+def reference_init_state(args, in_dim, out_dim, head_prefix, head_gain, recurrent, head_dims=None):
     """Initial weights with the reference's scheme AND its RNG consumption order, so that the same
     `torch.manual_seed` yields the same initial network as the reference (mlp.py:11-22, rnn.py:13-22,
     distributions.py:58-62, r_actor_critic.py:136-142): every nn.Linear / nn.GRU is constructed (default init
@@ -87,6 +87,12 @@ def reference_init_state(args, in_dim, out_dim, head_prefix, head_gain, recurren
                 (nn.init.orthogonal_ if args.use_orthogonal else nn.init.xavier_uniform_)(param)
             sd["rnn.rnn." + name] = param.data.clone()
         sd["rnn.norm.weight"], sd["rnn.norm.bias"] = torch.ones(H), torch.zeros(H)
+    if head_dims is not None:
+        # MultiDiscrete (act.py:27-33): one Categorical(H, d_j) per sub-action, constructed in order
+        for j, dj in enumerate(head_dims):
+            w, b = linear(H, dj, head_gain)
+            sd[f"{head_prefix}.{j}.linear.weight"], sd[f"{head_prefix}.{j}.linear.bias"] = w, b
+        return sd
     w, b = linear(H, out_dim, head_gain)
     sd[head_prefix + ".weight"], sd[head_prefix + ".bias"] = w, b
     return sd

@@ -121,6 +121,38 @@ extern "C" int mappo_actor_act(const float *params, const mappo_net_desc *desc, 
   return launch_forward<1>(a, as_stream(stream), "actor_act");
 }
 
+// get_actions of a MultiDiscrete policy: mappo_actor_act's kernel (same logits, bit for bit) with one sample / argmax per head
+extern "C" int mappo_actor_act_md(const float *params, const mappo_net_desc *desc, const float *obs, const float *avail,
+                                  const int32_t *head_dims, int32_t n_heads, int64_t B, int32_t deterministic, uint64_t seed,
+                                  uint64_t counter, const uint64_t *counter_dev, float *actions, float *logp, mappo_stream_t stream) {
+  MdHeads md;
+  if (int rc = check_md(desc, head_dims, n_heads, avail, "actor_act_md", md)) return rc;
+  MAPPO_REQUIRE(params && obs && actions && logp && B > 0, "actor_act_md: bad arguments");
+  MAPPO_CLEAR_STICKY();
+  FwdArgs a = {};
+  a.params = params; a.x = obs; a.actions = actions; a.logp = logp; a.desc = *desc;
+  a.B = B; a.deterministic = deterministic; a.seed = seed; a.counter = counter; a.counter_dev = counter_dev;
+  // the launch shape of launch_forward<1> for narrow inputs
+  const int64_t n_tiles = (B + TS - 1) / TS;
+  const int nw = fit_waves(a.desc, n_tiles >= 4 ? 4 : (n_tiles >= 2 ? 2 : 1));
+  a.off = net_offsets(a.desc);
+  a.map = lds_map(a.desc, nw);
+  const size_t lds_bytes = (size_t)a.map.total * sizeof(float);
+  MAPPO_REQUIRE(lds_bytes <= LDS_DYN_MAX, "actor_act_md: needs %zu B of LDS", lds_bytes);
+  int64_t nb = (n_tiles + nw - 1) / nw;
+  if (nb > NUM_CU) nb = NUM_CU;
+  dim3 grid((unsigned)nb), block(WAVE * nw);
+  const bool xw = a.desc.in_dim > 32;
+  hipStream_t st = as_stream(stream);
+  if (int rc = dispatch_relu_ln<1>(a.desc.use_relu != 0, a.desc.layer_N, [&](auto R, auto L) {
+        if (xw) return launch_kernel<mlp_forward_md_kernel<R.value, L.value, 1>, LDS_DYN_MAX, MAPPO_PROF_ACT>("actor_act_md", grid, block, lds_bytes, st, a, md);
+        return launch_kernel<mlp_forward_md_kernel<R.value, L.value, 0>, LDS_DYN_MAX, MAPPO_PROF_ACT>("actor_act_md", grid, block, lds_bytes, st, a, md);
+      }))
+    return rc;
+  MAPPO_CHECK_LAUNCH("actor_act_md");
+  return MAPPO_OK;
+}
+
 // ---- one wave per 16-sample tile (mlp_upd16.h) ---------------------------------------------------------------------
 #define UPD16_WAVES (UPD16_THREADS / WAVE)
 static size_t upd16_lds_floats(const mappo_net_desc &d, bool actor) {
@@ -372,6 +404,96 @@ extern "C" int mappo_critic_update(const float *params, const mappo_net_desc *de
   a.desc = *desc; a.B = B; a.v_old = v_old; a.returns = returns; a.active = active; a.vn_state = vn_state;
   a.mb_moments = mb_moments; a.partials = partials; a.cfg = *cfg; a.wide_ws = wide_ws; a.n_blocks = n_blocks;
   return launch_update<2>(a, as_stream(stream), "critic_update");
+}
+
+// ---- MultiDiscrete actor (multi-head loss) on the 16-sample-tile kernels ----
+// L16 of the multi-head actor: 33..64 inputs with a hidden layer drop the transposed W2' copy (L16::NOW2T), which is what makes
+// that shape fit
+static size_t upd16md_lds_floats(const mappo_net_desc &d) {
+  const bool w = d.in_dim > 32;
+  if (d.layer_N > 0) return w ? L16<1, 1, true, false, true>::TOTAL : L16<1, 1, false>::TOTAL;
+  return w ? L16<0, 1, true>::TOTAL : L16<0, 1, false>::TOTAL;
+}
+static_assert(L16<1, 1, true, false, true>::TOTAL * sizeof(float) <= UPD16_LDS_MAX, "the multi-head actor's widest layout must fit");
+
+extern "C" int mappo_actor_update_md(const float *params, const mappo_net_desc *desc, const float *obs, const int32_t *rows, int64_t B,
+                                     const float *avail, const int32_t *head_dims, int32_t n_heads, const float *actions,
+                                     const float *old_logp, const float *adv, const float *active, const double *mb_moments,
+                                     const mappo_ppo_cfg *cfg, float *slabs, int64_t slab_stride, int64_t slab_col0, double *partials,
+                                     float *wide_ws /*unused: in_dim <= 64*/, int32_t n_blocks, mappo_stream_t stream) {
+  (void)wide_ws;
+  MdHeads md;
+  if (int rc = check_md(desc, head_dims, n_heads, avail, "actor_update_md", md)) return rc;
+  MAPPO_REQUIRE(params && obs && actions && old_logp && adv && active && mb_moments && cfg && slabs && partials && B > 0,
+                "actor_update_md: bad arguments");
+  MAPPO_REQUIRE(n_blocks >= 0 && n_blocks <= NUM_CU, "actor_update_md: n_blocks %d outside [0,%d]", n_blocks, NUM_CU);
+  Upd16Args a16 = {};
+  UpdArgs &a = a16.u;
+  a.params = params; a.x = obs; a.rows = rows; a.slabs = slabs; a.slab_stride = slab_stride; a.slab_col0 = slab_col0;
+  a.desc = *desc; a.B = B; a.actions = actions; a.old_logp = old_logp; a.adv = adv; a.active = active;
+  a.mb_moments = mb_moments; a.partials = partials; a.cfg = *cfg; a.n_blocks = n_blocks;
+  a.off = net_offsets(a.desc);
+  MAPPO_REQUIRE(slab_col0 >= 0 && slab_col0 + a.off.total <= slab_stride, "actor_update_md: slab column range");
+  MAPPO_CLEAR_STICKY();
+  int nb = mappo_mlp_backward_slabs(B);
+  if (n_blocks > 0) nb = n_blocks < nb ? n_blocks : nb;
+  const size_t lds_bytes = upd16md_lds_floats(a.desc) * sizeof(float);
+  dim3 grid((unsigned)nb), block(WAVE * UPD16_WAVES);
+  const bool wide = a.desc.in_dim > 32;
+  if (int rc = dispatch_relu_ln<1>(a.desc.use_relu != 0, a.desc.layer_N, [&](auto R, auto L) {
+        return upd16md_inst<R.value, L.value>(wide, grid, block, lds_bytes, as_stream(stream), a16, md);
+      }))
+    return rc;
+  MAPPO_CHECK_LAUNCH("actor_update_md");
+  return MAPPO_OK;
+}
+
+// mappo_actor_critic_update for a MultiDiscrete actor.  Slab / partial rows per network: mappo_dual_update_slabs of the two
+// descriptors, as for the Discrete launch (an actor that the Discrete 16-sample-tile kernel cannot take — 33..64 inputs with a
+// hidden layer — gets that count of workgroups for each network).
+extern "C" int mappo_actor_critic_update_md(const float *actor_params, const mappo_net_desc *actor_desc, const float *obs,
+                                            const float *critic_params, const mappo_net_desc *critic_desc, const float *share_obs,
+                                            const int32_t *rows, int64_t B, const float *avail, const int32_t *head_dims,
+                                            int32_t n_heads, const float *actions, const float *old_logp, const float *adv,
+                                            const float *active, const float *v_old, const float *returns, const float *vn_state,
+                                            const double *mb_moments, const mappo_ppo_cfg *cfg, float *slabs, int64_t slab_stride,
+                                            int64_t actor_col0, int64_t critic_col0, double *actor_partials, double *critic_partials,
+                                            mappo_stream_t stream) {
+  MdHeads md;
+  if (int rc = check_md(actor_desc, head_dims, n_heads, avail, "actor_critic_update_md", md)) return rc;
+  if (int rc = check_desc(critic_desc, "actor_critic_update_md")) return rc;
+  MAPPO_REQUIRE(critic_desc->in_dim <= MAXD && critic_desc->layer_N <= 1, "actor_critic_update_md: critic in_dim %d > %d or layer_N %d > 1",
+                critic_desc->in_dim, MAXD, critic_desc->layer_N);
+  MAPPO_REQUIRE(actor_desc->layer_N == critic_desc->layer_N && actor_desc->use_relu == critic_desc->use_relu,
+                "actor_critic_update_md: actor and critic must share layer_N and the activation");
+  MAPPO_REQUIRE(critic_desc->out_dim == 1, "actor_critic_update_md: critic out_dim must be 1");
+  MAPPO_REQUIRE(actor_params && critic_params && obs && share_obs && actions && old_logp && adv && active && v_old && returns && mb_moments &&
+                    cfg && slabs && actor_partials && critic_partials && B > 0, "actor_critic_update_md: bad arguments");
+  MAPPO_REQUIRE(!cfg->use_valuenorm || vn_state, "actor_critic_update_md: use_valuenorm needs vn_state");
+  Dual16Args d = {};
+  UpdArgs &a = d.a.u, &c = d.c.u;
+  a.params = actor_params; a.x = obs; a.rows = rows; a.slabs = slabs; a.slab_stride = slab_stride; a.slab_col0 = actor_col0;
+  a.desc = *actor_desc; a.B = B; a.actions = actions; a.old_logp = old_logp; a.adv = adv; a.active = active;
+  a.mb_moments = mb_moments; a.partials = actor_partials; a.cfg = *cfg;
+  c.params = critic_params; c.x = share_obs; c.rows = rows; c.slabs = slabs; c.slab_stride = slab_stride; c.slab_col0 = critic_col0;
+  c.desc = *critic_desc; c.B = B; c.v_old = v_old; c.returns = returns; c.active = active; c.vn_state = vn_state;
+  c.mb_moments = mb_moments; c.partials = critic_partials; c.cfg = *cfg;
+  a.off = net_offsets(a.desc);
+  MAPPO_REQUIRE(actor_col0 >= 0 && actor_col0 + a.off.total <= slab_stride, "actor_critic_update_md: slab column range");
+  if (int rc = prep16(d.c, false, false, "actor_critic_update_md")) return rc;
+  MAPPO_CLEAR_STICKY();
+  if (upd16_eligible(*actor_desc, true)) upd16_split(a.desc, c.desc, B, d.nA, d.nC);
+  else d.nA = d.nC = mappo_dual_update_slabs(actor_desc, critic_desc, B);
+  if (d.nA < d.nC) { d.c.zero_row0 = d.nA; d.c.zero_row1 = d.nC; d.c.zero_col0 = actor_col0; d.c.zero_cols = a.off.total; d.c.zero_partials = actor_partials; }
+  if (d.nC < d.nA) { d.a.zero_row0 = d.nC; d.a.zero_row1 = d.nA; d.a.zero_col0 = critic_col0; d.a.zero_cols = c.off.total; d.a.zero_partials = critic_partials; }
+  const size_t la = upd16md_lds_floats(a.desc), lc = upd16_lds_floats(c.desc, false);
+  const size_t lds_bytes = (la > lc ? la : lc) * sizeof(float);
+  dim3 grid((unsigned)(d.nA + d.nC)), block(WAVE * UPD16_WAVES);
+  const bool wa = a.desc.in_dim > 32, wc = c.desc.in_dim > 32, relu = a.desc.use_relu != 0;
+  if (int rc = dispatch_relu_ln<1>(relu, a.desc.layer_N, [&](auto R, auto L) { return upd16mdd_inst<R.value, L.value>(wa, wc, grid, block, lds_bytes, as_stream(stream), d, md); }))
+    return rc;
+  MAPPO_CHECK_LAUNCH("actor_critic_update_md");
+  return MAPPO_OK;
 }
 
 // ---- actor + critic update in one launch --------------------------------------------------------------------------

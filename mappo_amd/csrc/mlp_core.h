@@ -310,6 +310,26 @@ __device__ __forceinline__ void categorical_act_mask(float *zl, int A, uint32_t 
   logp = zl[chosen] - lse;
 }
 
+// MultiDiscrete action spaces (act.py:27-33,65-76): the head output is n Categorical heads side by side, head j owning the
+// logits [lo_j, lo_j + dim[j]), lo_j = dim[0] + .. + dim[j - 1].  Passed to the multi-head kernels by value (n <= 4).
+struct MdHeads {
+  int n;
+  int dim[4];
+};
+// One lane walks the heads over its logits row zl[0, sum dim): head j is the Categorical epilogue above on its own segment with
+// Philox index (j << 32) | index (head 0 draws what a Discrete policy draws); actions / logp: the row's [n] outputs.
+__device__ __forceinline__ void categorical_act_heads(float *zl, const MdHeads &md, bool deterministic, uint64_t seed, uint64_t ctr,
+                                                      uint64_t index, float *actions, float *logp) {
+  int lo = 0;
+  for (int j = 0; j < md.n; ++j) {
+    float a, lp;
+    categorical_act_mask(zl + lo, md.dim[j], 0u, deterministic, seed, ctr, ((uint64_t)j << 32) | index, a, lp);
+    actions[j] = a;
+    logp[j] = lp;
+    lo += md.dim[j];
+  }
+}
+
 // head output (accumulator layout) -> tZ[s][a]
 __device__ __forceinline__ void head_to_tile(float *tZ, const f32x16 &z, int A, int l31, int half) {
   // rows a >= A go to column 32 of the row (the tile's padding column): an address select instead of 16 exec-mask regions

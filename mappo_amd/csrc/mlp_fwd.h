@@ -30,8 +30,9 @@ struct FwdArgs {
 
 // XW: 0 = in_dim <= 32, 1 = in_dim <= 64 (rows prefetched into registers), 2 = in_dim > 64 (K-chunked layer 1)
 // workgroup `bid` of `nb` workgroups that share the B rows (blockIdx / gridDim of a plain forward launch)
+// MODE 5 (MultiDiscrete): MODE 1 with one sample / argmax per head of `md` -> actions / logp [B][md->n]
 template <bool RELU, int LN, int MODE, int XW>
-__device__ __forceinline__ void forward_body(const FwdArgs &p, float *lds, const int bid, const int nb) {
+__device__ __forceinline__ void forward_body(const FwdArgs &p, float *lds, const int bid, const int nb, const MdHeads *md = nullptr) {
   constexpr bool WIDE = XW >= 1, XWIDE = XW == 2;
   const int n_waves = blockDim.x / WAVE;
   const NetOff &o = p.off;
@@ -93,6 +94,12 @@ __device__ __forceinline__ void forward_body(const FwdArgs &p, float *lds, const
         const int s = e / A, a = e - s * A;
         p.out[base * A + e] = tZ[s * TP + a];
       }
+    } else if (MODE == 5) {
+      if (lane < n_valid) {
+        const int64_t i = base + lane;
+        const uint64_t ctr = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);
+        categorical_act_heads(tZ + lane * TP, *md, p.deterministic != 0, p.seed, ctr, (uint64_t)i, p.actions + i * md->n, p.logp + i * md->n);
+      }
     } else {
       if (lane < n_valid) {
         const int64_t i = base + lane;
@@ -114,6 +121,13 @@ __global__ __launch_bounds__(256, 1) void mlp_forward_kernel(FwdArgs p) {
   forward_body<RELU, LN, MODE, XW>(p, lds, blockIdx.x, gridDim.x);
 }
 
+// get_actions of a MultiDiscrete policy (mappo_actor_act_md): the forward above with the per-head epilogue
+template <bool RELU, int LN, int XW>
+__global__ __launch_bounds__(256, 1) void mlp_forward_md_kernel(FwdArgs p, MdHeads md) {
+  extern __shared__ __align__(16) float lds[];
+  forward_body<RELU, LN, 5, XW>(p, lds, blockIdx.x, gridDim.x, &md);
+}
+
 // Fused rollout step (K7 + K8 + K1 in ONE launch): workgroups [0, nA) run the actor's get_actions, [nA, nA + nC) the
 // critic's get_values, the rest copy the env output the rows come from into the buffer slots (insert_core.h).  All
 // three read only their sources and write disjoint outputs, so there is nothing to order inside the launch.
@@ -129,6 +143,16 @@ __global__ __launch_bounds__(256, 1) void rollout_step_kernel(StepArgs s) {
   extern __shared__ __align__(16) float lds[];
   const int bid = blockIdx.x;
   if (bid < s.nA) forward16r_body<RELU, LN, 1>(s.a, lds, bid, s.nA);
+  else if (bid < s.nA + s.nC) forward16r_body<RELU, LN, 0>(s.c, lds, bid - s.nA, s.nC);
+  else insert_mpe_body(s.ins, bid - s.nA - s.nC, s.nI);
+}
+
+// The same step for a MultiDiscrete policy (mappo_rollout_step_md): the actor's workgroups sample every head of `md`
+template <bool RELU, int LN>
+__global__ __launch_bounds__(256, 1) void rollout_step_md_kernel(StepArgs s, MdHeads md) {
+  extern __shared__ __align__(16) float lds[];
+  const int bid = blockIdx.x;
+  if (bid < s.nA) forward16r_body<RELU, LN, 5>(s.a, lds, bid, s.nA, &md);
   else if (bid < s.nA + s.nC) forward16r_body<RELU, LN, 0>(s.c, lds, bid - s.nA, s.nC);
   else insert_mpe_body(s.ins, bid - s.nA - s.nC, s.nI);
 }

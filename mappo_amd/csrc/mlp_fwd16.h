@@ -138,10 +138,11 @@ __device__ __forceinline__ void forward16_tail(const FwdArgs &p, float *lds, con
 // no LDS except the logits tile of the sampling epilogue.  k-step (b, i) takes input / hidden feature 16 b + 4 q + i in every
 // layer.  (Rows of W1 are read up to 15 floats past in_dim — into the next row or the bias that follows W1 in the flat
 // parameter vector: finite values that meet zero inputs.)
-// head rows of lane (j, q) (MODE 0: block 0 only — the critic's row 0; MODE 1: two blocks of 16 actions; MODE 2: none)
+// head rows of lane (j, q) (MODE 0: block 0 only — the critic's row 0; MODE 1: two blocks of 16 actions; MODE 2: none;
+// MODE 5, MultiDiscrete: block 0 — the heads' logits side by side, at most 16)
 template <int MODE>
 struct Head16R {
-  static constexpr int NBH = MODE == 1 ? 2 : (MODE == 0 ? 1 : 0);     // head blocks of 16 outputs
+  static constexpr int NBH = MODE == 1 ? 2 : (MODE == 0 || MODE == 5 ? 1 : 0);     // head blocks of 16 outputs
   f32x4 wh[NBH > 0 ? NBH : 1][4];
   f32x4 bhv[NBH > 0 ? NBH : 1];
   // tile16r_step reads the head through these accessors only (Head16L in mlp_ep16l.h: the same operands from LDS)
@@ -175,11 +176,13 @@ __device__ __forceinline__ void head16r_load(Head16R<MODE> &hd, const float *P, 
 // ACT_TILE (MODE 1, the episode kernel that steps its environments itself): the action of tile row j also goes to act_tile[j]
 // in LDS, where the wave's environment lanes pick it up behind the closing wave_lds_sync.  TW / HD: where the weights come from
 // (Trunk16R / Head16R: registers; Trunk16L / Head16L: LDS) — same operands, same order, same arithmetic.
+// MODE 5 (MultiDiscrete): MODE 1 with the multi-head epilogue — the row's lane walks the heads of `md` over its logits row and
+// writes actions / logp [i][md->n]; block 0 of the head is computed exactly as in MODE 1, so one head reproduces Discrete.
 template <bool RELU, int LN, int MODE, bool DRAIN = false, bool ACT_TILE = false, class TW, class HD>
 __device__ __forceinline__ void tile16r_step(const FwdArgs &p, const TW &tw, const HD &hd, f32x4 (&x)[4],
                                              float *out, float *actions, float *logp, uint64_t ctr_base, const uint64_t *ctr_dev,
                                              float *tZ, const int64_t i, const bool ok, const int j, const int q,
-                                             float *act_tile = nullptr) {
+                                             float *act_tile = nullptr, const MdHeads *md = nullptr) {
   constexpr int NBH = HD::NBH;
   static_assert(HD::NBH == Head16R<MODE>::NBH, "head blocks follow the mode");
   const int D = p.desc.in_dim, A = p.desc.out_dim;
@@ -221,7 +224,12 @@ __device__ __forceinline__ void tile16r_step(const FwdArgs &p, const TW &tw, con
 #pragma unroll
         for (int r = 0; r < 4; ++r) { const int a = 16 * bo + 4 * q + r; if (a < A) tZ[j * TP + a] = z[bo][r]; }
       wave_lds_sync();
-      if (ok && q == 0) {
+      if constexpr (MODE == 5) {
+        if (ok && q == 0) {
+          const uint64_t ctr = ctr_base + (ctr_dev ? *ctr_dev : 0ull);
+          categorical_act_heads(tZ + j * TP, *md, p.deterministic != 0, p.seed, ctr, (uint64_t)i, actions + i * md->n, logp + i * md->n);
+        }
+      } else if (ok && q == 0) {
         const uint64_t ctr = ctr_base + (ctr_dev ? *ctr_dev : 0ull);
         float action, lp;
         categorical_act_lane(tZ + j * TP, A, p.avail ? p.avail + i * A : nullptr, p.deterministic != 0, p.seed, ctr, (uint64_t)i, action, lp);
@@ -243,7 +251,7 @@ __device__ __forceinline__ void tile16r_step(const FwdArgs &p, const TW &tw, con
 // layer.  (Rows of W1 are read up to 15 floats past in_dim — into the next row or the bias that follows W1 in the flat
 // parameter vector: finite values that meet zero inputs.)
 template <bool RELU, int LN, int MODE>
-__device__ __forceinline__ void forward16r_body(const FwdArgs &p, float *lds, const int bid, const int nb) {
+__device__ __forceinline__ void forward16r_body(const FwdArgs &p, float *lds, const int bid, const int nb, const MdHeads *md = nullptr) {
   const int n_waves = blockDim.x / WAVE;
   const NetOff &o = p.off;
   const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), j = lane & 15, q = lane >> 4;
@@ -279,7 +287,7 @@ __device__ __forceinline__ void forward16r_body(const FwdArgs &p, float *lds, co
 #pragma unroll
     for (int b = 0; b < 4; ++b) x[b] = xn[b];
     if (tile + (int64_t)nb * n_waves < n_tiles) load_x(tile + (int64_t)nb * n_waves, xn);      // (a wave with a second tile: its rows under this tile)
-    tile16r_step<RELU, LN, MODE>(p, tw, hd, x, p.out, p.actions, p.logp, p.counter, p.counter_dev, tZ, i, ok, j, q);
+    tile16r_step<RELU, LN, MODE>(p, tw, hd, x, p.out, p.actions, p.logp, p.counter, p.counter_dev, tZ, i, ok, j, q, nullptr, md);
   }
 }
 

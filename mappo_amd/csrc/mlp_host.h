@@ -40,6 +40,28 @@ static int check_desc(const mappo_net_desc *d, const char *who) {
 }
 static int check_desc_trunk(const mappo_net_desc *d, const char *who) { return check_desc_common(d, who); }
 
+// MultiDiscrete entry points (mappo_*_md): the limits of the multi-head kernels, checked on the host before anything is launched
+static int check_md(const mappo_net_desc *d, const int32_t *head_dims, int32_t n_heads, const float *avail, const char *who, MdHeads &md) {
+  MAPPO_REQUIRE(d, "%s: null desc", who);
+  MAPPO_REQUIRE(head_dims, "%s: null head_dims", who);
+  MAPPO_REQUIRE(n_heads >= 1 && n_heads <= 4, "%s: n_heads %d outside [1,4] (lane q of a sample's quad carries head q)", who, n_heads);
+  int sum = 0;
+  md = MdHeads{};
+  md.n = n_heads;
+  for (int j = 0; j < n_heads; ++j) {
+    MAPPO_REQUIRE(head_dims[j] >= 1, "%s: head_dims[%d] = %d, every head needs at least 1 action", who, j, head_dims[j]);
+    md.dim[j] = head_dims[j];
+    sum += head_dims[j];
+  }
+  MAPPO_REQUIRE(sum == d->out_dim, "%s: sum of head_dims %d != out_dim %d", who, sum, d->out_dim);
+  MAPPO_REQUIRE(d->out_dim <= 16, "%s: out_dim %d > 16 (the heads' logits share one 16-wide head tile)", who, d->out_dim);
+  MAPPO_REQUIRE(d->in_dim <= MAXD, "%s: in_dim %d > %d", who, d->in_dim, MAXD);
+  MAPPO_REQUIRE(d->layer_N <= 1, "%s: layer_N %d > 1", who, d->layer_N);
+  MAPPO_REQUIRE(!d->recurrent, "%s: recurrent policies are not built for MultiDiscrete spaces", who);
+  MAPPO_REQUIRE(!avail, "%s: MultiDiscrete spaces have no available_actions (avail must be NULL)", who);
+  return check_desc(d, who);
+}
+
 static int fit_waves(const mappo_net_desc &d, int want) {
   int nw = want;
   while (nw > 1 && (size_t)lds_map(d, nw).total * sizeof(float) > LDS_DYN_MAX) nw >>= 1;

@@ -112,14 +112,15 @@ int mappo_recurrent_step_dual_wide_(const float *actor_params, const mappo_net_d
 }
 
 // ---- fused rollout step (rollout_step_kernel): translation unit mlp_step.hip --------------------------------------
-extern "C" int mappo_rollout_step(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
-                                  const mappo_net_desc *critic_desc, const float *obs, int64_t obs_stride_n, int64_t obs_stride_m,
-                                  const float *share_obs, int64_t share_stride_n, int64_t share_stride_m, int32_t M, int64_t B,
-                                  const float *avail, int32_t deterministic, uint64_t seed, uint64_t counter,
-                                  const uint64_t *counter_dev, float *actions, float *logp, float *values, float *obs_dst,
-                                  float *share_dst, const float *rewards, int64_t rew_stride_n, int64_t rew_stride_m,
-                                  const uint8_t *dones, int64_t done_stride_n, int64_t done_stride_m, float *rew_dst,
-                                  float *mask_dst, int32_t centralized, mappo_stream_t stream) {
+// md != NULL: the MultiDiscrete step (mappo_rollout_step_md, narrow networks with layer_N <= 1: check_md): actions / logp [B][md->n]
+static int rollout_step_impl(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
+                             const mappo_net_desc *critic_desc, const float *obs, int64_t obs_stride_n, int64_t obs_stride_m,
+                             const float *share_obs, int64_t share_stride_n, int64_t share_stride_m, int32_t M, int64_t B,
+                             const float *avail, int32_t deterministic, uint64_t seed, uint64_t counter,
+                             const uint64_t *counter_dev, float *actions, float *logp, float *values, float *obs_dst,
+                             float *share_dst, const float *rewards, int64_t rew_stride_n, int64_t rew_stride_m,
+                             const uint8_t *dones, int64_t done_stride_n, int64_t done_stride_m, float *rew_dst,
+                             float *mask_dst, int32_t centralized, mappo_stream_t stream, const MdHeads *md) {
   if (int rc = check_desc(actor_desc, "rollout_step")) return rc;
   if (int rc = check_desc(critic_desc, "rollout_step")) return rc;
   MAPPO_REQUIRE((actor_desc->in_dim <= MAXD) == (critic_desc->in_dim <= MAXD) && actor_desc->in_dim <= 512 && critic_desc->in_dim <= 512,
@@ -216,12 +217,52 @@ extern "C" int mappo_rollout_step(const float *actor_params, const mappo_net_des
     s.nI = (int)(ni > NUM_CU ? NUM_CU : ni);              // (64 insert workgroups became the long pole of the launch beyond ~2 000 threads)
   }
   dim3 grid((unsigned)(s.nA + s.nC + s.nI)), block(WAVE * nw);
+  if (md) {
+    if (int rc = dispatch_relu_ln<1>(actor_desc->use_relu != 0, actor_desc->layer_N, [&](auto R, auto L) {
+          return launch_kernel<rollout_step_md_kernel<R.value, L.value>, LDS_DYN_MAX, MAPPO_PROF_ACT>("rollout_step_md", grid, block, lds_bytes, as_stream(stream), s, *md);
+        }))
+      return rc;
+    MAPPO_CHECK_LAUNCH("rollout_step_md");
+    return MAPPO_OK;
+  }
   if (int rc = dispatch_relu_ln(actor_desc->use_relu != 0, actor_desc->layer_N, [&](auto R, auto L) {
         return launch_kernel<rollout_step_kernel<R.value, L.value>, LDS_DYN_MAX, MAPPO_PROF_ACT>("rollout_step", grid, block, lds_bytes, as_stream(stream), s);
       }))
     return rc;
   MAPPO_CHECK_LAUNCH("rollout_step");
   return MAPPO_OK;
+}
+
+extern "C" int mappo_rollout_step(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
+                                  const mappo_net_desc *critic_desc, const float *obs, int64_t obs_stride_n, int64_t obs_stride_m,
+                                  const float *share_obs, int64_t share_stride_n, int64_t share_stride_m, int32_t M, int64_t B,
+                                  const float *avail, int32_t deterministic, uint64_t seed, uint64_t counter,
+                                  const uint64_t *counter_dev, float *actions, float *logp, float *values, float *obs_dst,
+                                  float *share_dst, const float *rewards, int64_t rew_stride_n, int64_t rew_stride_m,
+                                  const uint8_t *dones, int64_t done_stride_n, int64_t done_stride_m, float *rew_dst,
+                                  float *mask_dst, int32_t centralized, mappo_stream_t stream) {
+  return rollout_step_impl(actor_params, actor_desc, critic_params, critic_desc, obs, obs_stride_n, obs_stride_m, share_obs, share_stride_n,
+                           share_stride_m, M, B, avail, deterministic, seed, counter, counter_dev, actions, logp, values, obs_dst, share_dst,
+                           rewards, rew_stride_n, rew_stride_m, dones, done_stride_n, done_stride_m, rew_dst, mask_dst, centralized, stream,
+                           nullptr);
+}
+
+extern "C" int mappo_rollout_step_md(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
+                                     const mappo_net_desc *critic_desc, const float *obs, int64_t obs_stride_n, int64_t obs_stride_m,
+                                     const float *share_obs, int64_t share_stride_n, int64_t share_stride_m, int32_t M, int64_t B,
+                                     const float *avail, const int32_t *head_dims, int32_t n_heads, int32_t deterministic, uint64_t seed,
+                                     uint64_t counter, const uint64_t *counter_dev, float *actions, float *logp, float *values,
+                                     float *obs_dst, float *share_dst, const float *rewards, int64_t rew_stride_n, int64_t rew_stride_m,
+                                     const uint8_t *dones, int64_t done_stride_n, int64_t done_stride_m, float *rew_dst, float *mask_dst,
+                                     int32_t centralized, mappo_stream_t stream) {
+  MdHeads md;
+  if (int rc = check_md(actor_desc, head_dims, n_heads, avail, "rollout_step_md", md)) return rc;
+  if (int rc = check_desc(critic_desc, "rollout_step_md")) return rc;
+  MAPPO_REQUIRE(critic_desc->in_dim <= MAXD, "rollout_step_md: critic in_dim %d > %d", critic_desc->in_dim, MAXD);
+  return rollout_step_impl(actor_params, actor_desc, critic_params, critic_desc, obs, obs_stride_n, obs_stride_m, share_obs, share_stride_n,
+                           share_stride_m, M, B, nullptr, deterministic, seed, counter, counter_dev, actions, logp, values, obs_dst, share_dst,
+                           rewards, rew_stride_n, rew_stride_m, dones, done_stride_n, done_stride_m, rew_dst, mask_dst, centralized, stream,
+                           &md);
 }
 
 // ---- one rollout episode in one launch (rollout_episode_kernel) ---------------------------------------------------------------

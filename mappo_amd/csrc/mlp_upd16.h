@@ -39,8 +39,11 @@ __device__ __forceinline__ void static_for16(F &&f) { static_for_impl16(f, std::
 
 // LDS carve-up (floats), a compile-time function of the instantiation so that every LDS address is
 // "lane pattern (one VGPR) + immediate".  W1' is staged as [f][q * CP + t] (input feature k = q * C + t, C = ceil(D / 4)).
-template <int LN, int HEAD, bool WIDE, bool XL1 = false>
+template <int LN, int HEAD, bool WIDE, bool XL1 = false, bool NO_W2T = false>
 struct L16 {
+  // NO_W2T (the multi-head actor with 33..64 inputs and a hidden layer, whose tiles would not fit otherwise): no transposed
+  // copy of W2'; the backward-data product reads W2' itself, one scalar operand per MFMA (hidden_bwd16_nt)
+  static constexpr bool NOW2T = NO_W2T;
   // XL1: layer 1 runs in its own kernels (mlp_wide16.h forward, wide_l1_bwd_kernel weight gradient): no W1 copy, no xhat0 tile
   // The three matrices are staged in FRAGMENT order: the 16 x 16 block (bo, b) is 256 consecutive floats, lane (n, q) owning
   // M[16 bo + n][4 consecutive k of its k-step group] at float offset 4 * lane, so the A operands of four MFMAs are ONE 16-byte
@@ -51,7 +54,7 @@ struct L16 {
   static constexpr int W1 = 0;                                    // W1' block (bo, tc): rows 16 bo + n, columns q CP + 4 tc + i
   static constexpr int W2 = W1 + (XL1 ? 0 : HID * 4 * CP);        // W2' block (bo, b): rows 16 bo + n, columns 16 b + 4 q + i (forward A operand)
   static constexpr int W2T = W2 + (LN > 0 ? HID * HID : 0);       // W2'^T, the same with rows = k, columns = f (backward-data A operand)
-  static constexpr int WH = W2T + (LN > 0 ? HID * HID : 0);       // actor: Wh' [action][k] (16 rows, stride HS16) | critic: Wh' [k]
+  static constexpr int WH = W2T + (LN > 0 && !NO_W2T ? HID * HID : 0);       // actor: Wh' [action][k] (16 rows, stride HS16) | critic: Wh' [k]
   __host__ __device__ static constexpr int w1_at(int f, int r) { return ((f >> 4) * NT + ((r % CP) >> 2)) * 256 + ((r / CP) * 16 + (f & 15)) * 4 + (r & 3); }
   static constexpr int B1 = WH + (HEAD == 1 ? 16 * HS16 : HID), B2 = B1 + HID, BH = B2 + HID;      // folded biases
   static constexpr int FN_W = BH + 16, FN_B = FN_W + HID, G1 = FN_B + HID, T1 = G1 + HID, G2 = T1 + HID, T2 = G2 + HID;   // raw affine vectors
@@ -189,6 +192,28 @@ __device__ __forceinline__ void hidden_bwd16(f32x4 (&out)[4], const f32x4 (&dz)[
   hidden_fwd16(out, dz, sWT, n, q);
 }
 
+// The same product from the forward copy W' (fragment order): A operand W'[16 b + 4 q + i][16 bo + n], one 4-byte read per MFMA,
+// the k-steps in hidden_bwd16's order.  This is the UNTUNED path of one shape class (L16::NOW2T: the multi-head actor with 33..64
+// inputs and a hidden layer): 64 scalar LDS reads per tile where hidden_bwd16 issues 16 16-byte ones, the four lanes n, n + 4, n + 8,
+// n + 12 of a read on the same bank; and in the dual launch that shape gets mappo_dual_update_slabs' pair-kernel count of workgroups
+// (at most 128 per network, mlp.hip).  Measured 118 us per dual launch at 76 800 rows against 94 us for the 21-input actor
+// (DESIGN.md); a layout with room for W2'^T, or fewer waves per workgroup, is what a tuned version would need.
+__device__ __forceinline__ void hidden_bwd16_nt(f32x4 (&out)[4], const f32x4 (&dz)[4], const float *sW, int n, int q) {
+#pragma unroll
+  for (int bo = 0; bo < 4; ++bo) { out[bo][0] = 0.f; out[bo][1] = 0.f; out[bo][2] = 0.f; out[bo][3] = 0.f; }
+  const float *base = sW + ((n >> 2) * 16 + 4 * q) * 4 + (n & 3);      // frag64_at(16 b + 4 q + i, 16 bo + n) - (4 b + bo) * 256 - 4 i
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float a[4];
+#pragma unroll
+      for (int bo = 0; bo < 4; ++bo) a[bo] = base[(4 * b + bo) * 256 + 4 * i];
+#pragma unroll
+      for (int bo = 0; bo < 4; ++bo) out[bo] = mfma16(a[bo], dz[b][i], out[bo]);
+    }
+}
+
 // G[bf][bk] (rows f = 16 bf + 4 q + i, columns k = 16 bk + n) += sum_s UA[s][16 bf + ..] * UB[s][16 bk + ..].
 // gb[bf] += the lane's A operands (dz[16 bf + n] of samples 4 q + j): per-lane partial sums of the bias gradient (reduced
 // over q once, in the epilogue) — no separate pass over the dz tile.
@@ -232,9 +257,10 @@ struct Prefetch16 {
 // 16-byte aligned x): the tile is ONE contiguous 16 x D block, fetched as fully coalesced 16-byte buffer loads — the
 // descriptor's bounds check returns 0 beyond the block, so there is no per-lane clamp — and redistributed through the
 // wave's xhat0 tile at the commit.  Gathered rows / ragged last tile: lane (n, q) fetches its own features.
-template <int HEAD, bool WIDE>
+// MD (multi-head actor, K heads): actions / old_logp are [.][K]; lane (n, q) fetches head min(q, K - 1)'s pair of its sample.
+template <int HEAD, bool WIDE, bool MD = false>
 __device__ __forceinline__ void prefetch16(Prefetch16<WIDE> &pf, const UpdArgs &p, int64_t tile, int64_t n_tiles, int D, int C, int A,
-                                           int lane, int n, int q) {
+                                           int lane, int n, int q, int K = 1) {
   constexpr int NV = WIDE ? 16 : 8;
   int64_t base = tile * 16;
   int nv = (tile < n_tiles) ? (int)min((int64_t)16, p.B - base) : 0;
@@ -257,7 +283,10 @@ __device__ __forceinline__ void prefetch16(Prefetch16<WIDE> &pf, const UpdArgs &
       const f32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rx, lane * 16, 1024 * j, 0);
       pf.xv[4 * j + 0] = t[0]; pf.xv[4 * j + 1] = t[1]; pf.xv[4 * j + 2] = t[2]; pf.xv[4 * j + 3] = t[3];
     }
-    if constexpr (HEAD == 1) {
+    if constexpr (HEAD == 1 && MD) {
+      const int e = n * K + min(q, K - 1);                       // the tile's [16][K] block is contiguous
+      pf.f0 = (p.actions + base * K)[e]; pf.f1 = (p.old_logp + base * K)[e]; pf.f2 = (p.adv + base)[n]; pf.f3 = (p.active + base)[n];
+    } else if constexpr (HEAD == 1) {
       pf.f0 = (p.actions + base)[n]; pf.f1 = (p.old_logp + base)[n]; pf.f2 = (p.adv + base)[n]; pf.f3 = (p.active + base)[n];
       if (p.avail) {
         // availability of action 4 i + q: one bounds-checked dword per i (0 = unavailable | beyond A: masked below)
@@ -281,7 +310,10 @@ __device__ __forceinline__ void prefetch16(Prefetch16<WIDE> &pf, const UpdArgs &
   const float *src = p.x + row * D;
 #pragma unroll
   for (int t = 0; t < NV; ++t) pf.xv[t] = src[min(qo * C + t, D - 1)];      // unconditional clamped loads, masked at the commit
-  if constexpr (HEAD == 1) {
+  if constexpr (HEAD == 1 && MD) {
+    const int64_t e = row * K + min(q, K - 1);
+    pf.f0 = p.actions[e]; pf.f1 = p.old_logp[e]; pf.f2 = p.adv[row]; pf.f3 = p.active[row];
+  } else if constexpr (HEAD == 1) {
     pf.f0 = p.actions[row]; pf.f1 = p.old_logp[row]; pf.f2 = p.adv[row]; pf.f3 = p.active[row];
     if (p.avail) {
       const float *av = p.avail + row * A;
@@ -387,6 +419,73 @@ __device__ __forceinline__ void actor_loss_quad(f32x4 &z, int A, int q, uint32_t
   }
 }
 
+// The same objective for a MultiDiscrete policy (act.py:139-152, r_mappo.py:124-141): the 16 logits of a sample are md.n heads
+// side by side.  Per head j the masked max / sum-exp / entropy / chosen-logit reductions run over the quad restricted to the
+// head's index range [lo_j, lo_j + dim_j), then r_j = exp(lp_j - old_lp_j), the clip decision and the gradient
+// dlogp_j (1[a] - p) + (ce / K) p (l + H_j) on the head's logits; logits >= A get zero.  Lane q of the quad carries head q's
+// action (head-local index) and old log-prob (act_q / old_lp_q), handed to the other three lanes by an exact quad sum.
+// Partials: lacc = {sum w sum_j s_j, sum w (1/K) sum_j H_j, sum (1/K) sum_j r_j}.
+__device__ __forceinline__ void actor_loss_quad_md(f32x4 &z, const MdHeads &md, int q, float act_q, float old_lp_q, float adv, float active,
+                                                   bool count, const mappo_ppo_cfg &cfg, float scale_pi, float (&lacc)[3]) {
+  const float clip = cfg.clip_param;
+  const float w = cfg.use_policy_active_masks ? active : 1.f;
+  const float inv_k = 1.f / (float)md.n;
+  const float ce = cfg.entropy_coef * w * scale_pi * inv_k;
+  f32x4 g = {0.f, 0.f, 0.f, 0.f};
+  float s_sum = 0.f, h_sum = 0.f, r_sum = 0.f;
+  int lo = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (j < md.n) {                                        // wave-uniform
+      const int hi = lo + md.dim[j];
+      const int act = lo + (int)quad_sum16(q == j ? act_q : 0.f);
+      const float old_lp = quad_sum16(q == j ? old_lp_q : 0.f);
+      bool in[4];
+      float zm = -FLT_MAX;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        in[i] = 4 * i + q >= lo && 4 * i + q < hi;
+        if (in[i]) zm = fmaxf(zm, z[i]);
+      }
+      const float zmax = quad_max16(zm);
+      float e[4], se = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { e[i] = in[i] ? fast_exp(z[i] - zmax) : 0.f; se += e[i]; }
+      se = quad_sum16(se);
+      const float log_se = fast_log(se), inv_se = __builtin_amdgcn_rcpf(se);
+      float hp = 0.f, za = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float l_ = (z[i] - zmax) - log_se;
+        if (in[i]) hp += (e[i] * inv_se) * fmaxf(l_, -FLT_MAX);
+        if (in[i] && 4 * i + q == act) za = z[i];
+      }
+      const float H = -quad_sum16(hp);
+      const float z_act = quad_sum16(za);                   // one lane / register of the sample is non-zero: exact
+      const float logp = (z_act - zmax) - log_se;
+      const float ratio = fast_exp(logp - old_lp);
+      const float s1 = ratio * adv, s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * adv;
+      const float dlogp = (s1 <= s2) ? -(w * scale_pi) * adv * ratio : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float l_ = (z[i] - zmax) - log_se;
+        const float pa = e[i] * inv_se;
+        if (in[i] && count) g[i] = dlogp * ((4 * i + q == act ? 1.f : 0.f) - pa) + ce * pa * (l_ + H);
+      }
+      s_sum += fminf(s1, s2);
+      h_sum += H;
+      r_sum += ratio;
+      lo = hi;
+    }
+  }
+  z = g;
+  if (count && q == 0) {
+    lacc[0] += w * s_sum;
+    lacc[1] += w * (h_sum * inv_k);
+    lacc[2] += r_sum * inv_k;
+  }
+}
+
 // critic_loss_lane with float statistics (a lane sees a handful of samples; the cross-lane sums are taken in double)
 __device__ __forceinline__ float critic_loss16(float v, float vo, float ret, float active, const mappo_ppo_cfg &cfg, const LossScales &ls,
                                                bool count, float (&lacc)[3]) {
@@ -447,13 +546,17 @@ __device__ __forceinline__ void copy16(float *dst, const float *src, int n) {
 }
 
 // Workgroup `bid` of the `nb` workgroups that share this network's rows.  512 threads (8 waves, 2 per SIMD).
-template <bool RELU, int LN, int HEAD, bool WIDE, bool XL1 = false>
-__device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, const int bid, const int nb) {
+// MD: the actor head (HEAD 1) is the md->n Categorical heads of a MultiDiscrete policy (actor_loss_quad_md; actions / old_logp [.][K]).
+template <bool RELU, int LN, int HEAD, bool WIDE, bool XL1 = false, bool MD = false>
+__device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, const int bid, const int nb, const MdHeads *md = nullptr) {
   static_assert(LN <= 1 && (HEAD == 1 || HEAD == 2 || HEAD == 3), "update16: layer_N <= 1; heads: actor loss, critic loss, trunk (gradient in)");
   static_assert(!XL1 || WIDE, "XL1 uses the 16-register prefetch block");
+  static_assert(!MD || (HEAD == 1 && !XL1), "update16: the multi-head loss is the narrow actor's");
   constexpr int NV = WIDE ? 16 : 8, NBK = WIDE ? 4 : 2;
   const UpdArgs &p = P.u;
-  typedef L16<LN, HEAD, WIDE, XL1> M;
+  typedef L16<LN, HEAD, WIDE, XL1, MD && WIDE && (LN > 0)> M;
+  int K = 1;
+  if constexpr (MD) K = md->n;
   // XL1 workspace (mappo_wide_workspace_floats): dz1 [64][B] feature-major | mean0 [B] | rstd0 [B] | z1 [B][64]
   const float *z1 = XL1 ? p.wide_ws + 66 * ((p.B + 15) & ~(int64_t)15) : nullptr;      // wide16_z1_offset (mlp_wide16.h)
   const NetOff &o = p.off;
@@ -470,7 +573,7 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
   const int64_t tile0 = (int64_t)wave * nb + bid;          // remainder of the last round spreads over all CUs
   Prefetch16<WIDE> pf;
   if constexpr (XL1) prefetch16x<HEAD>(pf, p, z1, tile0, n_tiles, A, n, q);
-  else prefetch16<HEAD, WIDE>(pf, p, tile0, n_tiles, D, C, A, lane, n, q);
+  else prefetch16<HEAD, WIDE, MD>(pf, p, tile0, n_tiles, D, C, A, lane, n, q, K);
   STAMP_DECL
 
   // ---- stage the network: W' = W * gamma_in (columns), b' = b + W beta_in.  Thread (f8 = tid / 8, part = tid % 8) owns the
@@ -542,7 +645,7 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
       if constexpr (LN > 0) {
         const float wsc = w2r[j] * lds[M::G1 + k];
         lds[M::W2 + frag64_at(f8, k)] = wsc;
-        lds[M::W2T + frag64_at(k, f8)] = wsc;
+        if constexpr (!M::NOW2T) lds[M::W2T + frag64_at(k, f8)] = wsc;
         pb2 += w2r[j] * lds[M::T1 + k];
       }
       if constexpr (HEAD == 1) {
@@ -727,7 +830,7 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
     // next tile, under this tile's MFMAs (issued after the loss instead, the prefetch registers live through the
     // register-hungry backward pass only — but that is where the pressure peaks: 106 spilled registers, measured)
     if constexpr (XL1) prefetch16x<HEAD>(pf, p, z1, tile + tile_stride, n_tiles, A, n, q);
-    else prefetch16<HEAD, WIDE>(pf, p, tile + tile_stride, n_tiles, D, C, A, lane, n, q);
+    else prefetch16<HEAD, WIDE, MD>(pf, p, tile + tile_stride, n_tiles, D, C, A, lane, n, q, K);
     f32x4 dh[HEAD == 3 ? 4 : 1];
     if constexpr (HEAD == 3) {
       // d(trunk output): this tile's values were fetched a tile ago; the next tile's 16 dwords per lane (64-byte segments)
@@ -834,7 +937,8 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
           for (int i = 0; i < 4; ++i) z = mfma16(a[i], xh[b][i], z);
         }
       }
-      actor_loss_quad(z, A, q, cdead, (int)c0, c1, c2, c3, live, p.cfg, ls.scale_pi, lacc);
+      if constexpr (MD) actor_loss_quad_md(z, *md, q, c0, c1, c2, c3, live, p.cfg, ls.scale_pi, lacc);
+      else actor_loss_quad(z, A, q, cdead, (int)c0, c1, c2, c3, live, p.cfg, ls.scale_pi, lacc);
 #pragma unroll
       for (int i = 0; i < 4; ++i) Udl[n * DLS16 + 4 * i + q] = z[i];
       wave_lds_sync();
@@ -867,7 +971,8 @@ __device__ __forceinline__ void update16_body(const Upd16Args &P, float *lds, co
       dw_accum16<4, 4>(gW2, gB2, Ut, RS16, Uh, RS16, n, q);
       STAMP(8);   // dW2
       f32x4 d1[4];
-      hidden_bwd16(d1, dx, lds + M::W2T, n, q);
+      if constexpr (M::NOW2T) hidden_bwd16_nt(d1, dx, lds + M::W2, n, q);
+      else hidden_bwd16(d1, dx, lds + M::W2T, n, q);
 #pragma unroll
       for (int b = 0; b < 4; ++b) { xh[b] = ld4(Uh + n * RS16 + 16 * b + 4 * q); dx[b] = d1[b]; }
       wave_lds_sync();
@@ -1092,5 +1197,19 @@ __global__ __launch_bounds__(512, 2) void mlp_update16_dual_kernel(Dual16Args d)
   extern __shared__ __align__(16) float lds[];
   const int bid = blockIdx.x;
   if (bid < d.nA) update16_body<RELU, LN, 1, WIDE_A>(d.a, lds, bid, d.nA);
+  else update16_body<RELU, LN, 2, WIDE_C>(d.c, lds, bid - d.nA, d.nC);
+}
+
+// The MultiDiscrete actor (mappo_actor_update_md / mappo_actor_critic_update_md): the same kernels with the multi-head loss
+template <bool RELU, int LN, bool WIDE>
+__global__ __launch_bounds__(512, 2) void mlp_update16_md_kernel(Upd16Args a, MdHeads md) {
+  extern __shared__ __align__(16) float lds[];
+  update16_body<RELU, LN, 1, WIDE, false, true>(a, lds, blockIdx.x, gridDim.x, &md);
+}
+template <bool RELU, int LN, bool WIDE_A, bool WIDE_C>
+__global__ __launch_bounds__(512, 2) void mlp_update16_md_dual_kernel(Dual16Args d, MdHeads md) {
+  extern __shared__ __align__(16) float lds[];
+  const int bid = blockIdx.x;
+  if (bid < d.nA) update16_body<RELU, LN, 1, WIDE_A, false, true>(d.a, lds, bid, d.nA, &md);
   else update16_body<RELU, LN, 2, WIDE_C>(d.c, lds, bid - d.nA, d.nC);
 }

@@ -6,6 +6,30 @@
 
 static_assert(L16<0, 1, false>::LDS_CAP * 4 == UPD16_LDS_MAX, "L16::LDS_CAP is UPD16_LDS_MAX in floats");
 
+#ifdef MLP_UPD_MD
+// the MultiDiscrete actor's kernels (mlp_update16_md_kernel, mlp_update16_md_dual_kernel): translation units mlp_upd16md_r*_l*.hip
+template <bool R, int L, bool W>
+static int upd16md_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Upd16Args &a, const MdHeads &md) {
+  return launch_kernel<mlp_update16_md_kernel<R, L, W>, UPD16_LDS_MAX, MAPPO_PROF_MLP_BWD>("actor_update_md", grid, block, lds_bytes, st, a, md);
+}
+template <bool R, int L>
+int upd16md_inst(bool wide, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Upd16Args &a, const MdHeads &md) {
+  return wide ? upd16md_launch<R, L, true>(grid, block, lds_bytes, st, a, md) : upd16md_launch<R, L, false>(grid, block, lds_bytes, st, a, md);
+}
+template int upd16md_inst<MLP_UPD_RELU, MLP_UPD_LN>(bool, dim3, dim3, size_t, hipStream_t, const Upd16Args &, const MdHeads &);
+
+template <bool R, int L, bool WA, bool WC>
+static int upd16mdd_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Dual16Args &d, const MdHeads &md) {
+  return launch_kernel<mlp_update16_md_dual_kernel<R, L, WA, WC>, UPD16_LDS_MAX, MAPPO_PROF_MLP_BWD>("actor_critic_update_md", grid, block, lds_bytes, st, d, md);
+}
+template <bool R, int L>
+int upd16mdd_inst(bool wa, bool wc, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Dual16Args &d, const MdHeads &md) {
+  if (wa) return wc ? upd16mdd_launch<R, L, true, true>(grid, block, lds_bytes, st, d, md) : upd16mdd_launch<R, L, true, false>(grid, block, lds_bytes, st, d, md);
+  return wc ? upd16mdd_launch<R, L, false, true>(grid, block, lds_bytes, st, d, md) : upd16mdd_launch<R, L, false, false>(grid, block, lds_bytes, st, d, md);
+}
+template int upd16mdd_inst<MLP_UPD_RELU, MLP_UPD_LN>(bool, bool, dim3, dim3, size_t, hipStream_t, const Dual16Args &, const MdHeads &);
+#else
+
 template <bool R, int L, int HEAD, bool W>
 static int upd16_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Upd16Args &a) {
   return launch_kernel<mlp_update16_kernel<R, L, HEAD, W>, UPD16_LDS_MAX, MAPPO_PROF_MLP_BWD>("update16", grid, block, lds_bytes, st, a);
@@ -39,3 +63,4 @@ int upd16x_inst(int head, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s
   return head == 1 ? upd16x_launch<R, L, 1>(grid, block, lds_bytes, st, a) : upd16x_launch<R, L, 2>(grid, block, lds_bytes, st, a);
 }
 template int upd16x_inst<MLP_UPD_RELU, MLP_UPD_LN>(int, dim3, dim3, size_t, hipStream_t, const Upd16Args &);
+#endif  // MLP_UPD_MD

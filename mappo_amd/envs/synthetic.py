@@ -8,20 +8,28 @@ Observations ~ N(0,1); rewards ~ N(0,1) shared by the agents of a thread (shared
 every env reports done on each `episode_length`-th step (MPE time limit, environment.py:179-185)."""
 import torch
 
-from ..utils.util import Discrete
+from ..utils.util import Discrete, MultiDiscrete
 
 
 class SyntheticMPEEnv:
     graph_safe = True      # step() is a fixed sequence of device ops: the runner may capture an episode into a hipGraph
     consumes_actions = False   # the synthetic dynamics ignore the actions: the runner need not build one-hot actions
 
-    def __init__(self, n_rollout_threads, num_agents=3, obs_dim=18, n_actions=5, episode_length=25, seed=1, device="cuda"):
+    def __init__(self, n_rollout_threads, num_agents=3, obs_dim=18, n_actions=5, episode_length=25, seed=1, device="cuda",
+                 action_dims=None):
+        """action_dims = (d_0, d_1, ...): the agents' action space is MultiDiscrete([[0, d_0 - 1], [0, d_1 - 1], ...]) (the
+        simple_reference shape is (5, 10)) and actions_env is the heads' one-hots side by side; None: Discrete(n_actions)."""
+        if action_dims is not None:
+            n_actions = int(sum(action_dims))
         self.N, self.M, self.D, self.A, self.T = n_rollout_threads, num_agents, obs_dim, n_actions, episode_length
         self.device = torch.device(device)
         self.seed = seed
         self.observation_space = [[obs_dim] for _ in range(num_agents)]
         self.share_observation_space = [[obs_dim * num_agents] for _ in range(num_agents)]
-        self.action_space = [Discrete(n_actions) for _ in range(num_agents)]
+        if action_dims is not None:
+            self.action_space = [MultiDiscrete([[0, int(d) - 1] for d in action_dims]) for _ in range(num_agents)]
+        else:
+            self.action_space = [Discrete(n_actions) for _ in range(num_agents)]
         self.t = 0
         self._pool = None
         self._done_true = torch.ones(self.N, self.M, dtype=torch.bool, device=self.device)

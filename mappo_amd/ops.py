@@ -252,6 +252,70 @@ def rollout_step(actor_params, actor_desc, critic_params, critic_desc, obs, shar
     _lib.check(rc, "mappo_rollout_step")
 
 
+# ---- MultiDiscrete action spaces: one Categorical head per sub-action (mappo_*_md) ---------------------------------
+def _heads(head_dims):
+    arr = (C.c_int32 * len(head_dims))(*[int(d) for d in head_dims])
+    return arr, len(head_dims)
+
+
+def actor_act_md(params, desc, obs, head_dims, B, deterministic, seed, counter, actions, logp, counter_dev=None, avail=None):
+    """get_actions of a MultiDiscrete policy: actions / logp [B, K] (mappo_actor_act_md)."""
+    arr, K = _heads(head_dims)
+    rc = _lib.load().mappo_actor_act_md(_ptr(params), C.byref(desc), _ptr(obs), _ptr(avail, allow_none=True), arr, K, int(B),
+                                        int(bool(deterministic)), int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
+                                        _ptr(counter_dev, torch.int64, allow_none=True), _ptr(actions), _ptr(logp), _stream())
+    _lib.check(rc, "mappo_actor_act_md")
+
+
+def rollout_step_md(actor_params, actor_desc, critic_params, critic_desc, obs, share_obs, M, B, head_dims, deterministic, seed, counter,
+                    counter_dev, actions, logp, values, insert=None, avail=None):
+    """rollout_step for a MultiDiscrete policy (actions / logp [B, K]); arguments as rollout_step."""
+    ot, osn, osm = obs
+    st, ssn, ssm = share_obs
+    arr, K = _heads(head_dims)
+    if insert is None:
+        ins = (None, None, None, 0, 0, None, 0, 0, None, None, 0)
+    else:
+        rt, rsn, rsm = insert["rewards"]
+        dt, dsn, dsm = insert["dones"]
+        ins = (C.c_void_p(insert["obs_dst"].data_ptr()), C.c_void_p(insert["share_dst"].data_ptr()), C.c_void_p(rt.data_ptr()), int(rsn), int(rsm),
+               C.c_void_p(dt.data_ptr()), int(dsn), int(dsm), C.c_void_p(insert["rew_dst"].data_ptr()), C.c_void_p(insert["mask_dst"].data_ptr()),
+               int(bool(insert["centralized"])))
+    rc = _lib.load().mappo_rollout_step_md(_ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc),
+                                           C.c_void_p(ot.data_ptr()), int(osn), int(osm), C.c_void_p(st.data_ptr()), int(ssn), int(ssm), int(M),
+                                           int(B), _ptr(avail, allow_none=True), arr, K, int(bool(deterministic)), int(seed) & (2 ** 64 - 1),
+                                           int(counter) & (2 ** 64 - 1), _ptr(counter_dev, torch.int64, allow_none=True),
+                                           _ptr(actions, allow_none=True), _ptr(logp, allow_none=True), _ptr(values), *ins, _stream())
+    _lib.check(rc, "mappo_rollout_step_md")
+
+
+def actor_update_md(params, desc, obs, rows, B, head_dims, actions, old_logp, adv, active, mb_moments, cfg, slabs, slab_stride,
+                    slab_col0, partials, n_blocks=0, avail=None):
+    """actor_update for a MultiDiscrete policy: actions / old_logp [., K] in buffer order (mappo_actor_update_md)."""
+    arr, K = _heads(head_dims)
+    rc = _lib.load().mappo_actor_update_md(_ptr(params), C.byref(desc), _ptr(obs), _ptr(rows, torch.int32, allow_none=True), int(B),
+                                           _ptr(avail, allow_none=True), arr, K, _ptr(actions), _ptr(old_logp), _ptr(adv), _ptr(active),
+                                           _ptr(mb_moments, torch.float64), C.byref(cfg), _ptr(slabs), int(slab_stride), int(slab_col0),
+                                           _ptr(partials, torch.float64), None, int(n_blocks), _stream())
+    _lib.check(rc, "mappo_actor_update_md")
+
+
+def actor_critic_update_md(actor_params, actor_desc, obs, critic_params, critic_desc, share_obs, rows, B, head_dims, actions, old_logp,
+                           adv, active, v_old, returns, vn_state, mb_moments, cfg, slabs, slab_stride, actor_col0, critic_col0,
+                           actor_partials, critic_partials, avail=None):
+    """actor_critic_update for a MultiDiscrete policy (mappo_actor_critic_update_md); slab / partial rows per network:
+    dual_update_slabs(actor_desc, critic_desc, B)."""
+    arr, K = _heads(head_dims)
+    rc = _lib.load().mappo_actor_critic_update_md(_ptr(actor_params), C.byref(actor_desc), _ptr(obs), _ptr(critic_params),
+                                                  C.byref(critic_desc), _ptr(share_obs), _ptr(rows, torch.int32, allow_none=True), int(B),
+                                                  _ptr(avail, allow_none=True), arr, K, _ptr(actions), _ptr(old_logp), _ptr(adv),
+                                                  _ptr(active), _ptr(v_old), _ptr(returns), _ptr(vn_state, allow_none=True),
+                                                  _ptr(mb_moments, torch.float64), C.byref(cfg), _ptr(slabs), int(slab_stride),
+                                                  int(actor_col0), int(critic_col0), _ptr(actor_partials, torch.float64),
+                                                  _ptr(critic_partials, torch.float64), _stream())
+    _lib.check(rc, "mappo_actor_critic_update_md")
+
+
 def _strided(t, dtype):
     """Pointer of a (possibly strided) device view, for the entry points that take explicit strides."""
     if not t.is_cuda:

@@ -21,6 +21,10 @@ class Runner(_SharedRunner):
         from mappo_amd.algorithms.r_mappo.algorithm.rMAPPOPolicy import R_MAPPOPolicy as Policy
         self.policy, self.trainer, self.buffer = [], [], []
         for agent_id in range(self.num_agents):
+            if self.envs.action_space[agent_id].__class__.__name__ == "MultiDiscrete":
+                raise NotImplementedError("MultiDiscrete action space under the separated runner (share_policy = False): the K-wide action "
+                                          "columns are built for the shared MPERunner only")
+        for agent_id in range(self.num_agents):
             share_space = self.envs.share_observation_space[agent_id] if self.use_centralized_V else self.envs.observation_space[agent_id]
             self.policy.append(Policy(self.all_args, self.envs.observation_space[agent_id], share_space, self.envs.action_space[agent_id],
                                       device=self.device))

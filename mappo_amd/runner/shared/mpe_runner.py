@@ -13,6 +13,19 @@ import torch
 from .base_runner import Runner, _t2n, env_takes_device_actions
 
 
+def onehot_actions(actions, action_space, eye=None):
+    """actions_env of mpe_runner.py:111-121 on the device: Discrete -> np.eye(n)[actions] ([N, M, n]); MultiDiscrete -> the
+    heads' one-hots side by side ([N, M, sum d_j]).  actions: [N, M, K] indices (any dtype)."""
+    from mappo_amd.utils.util import head_dims_of
+    a = actions.long()
+    if action_space.__class__.__name__ == "MultiDiscrete":
+        dims = head_dims_of(action_space)
+        return torch.cat([torch.eye(d, device=a.device)[a[..., j]] for j, d in enumerate(dims)], dim=-1)
+    if eye is None:
+        eye = torch.eye(action_space.n, device=a.device)
+    return eye[a.view(a.shape[0], a.shape[1])]
+
+
 class MPERunner(Runner):
     def __init__(self, config):
         super(MPERunner, self).__init__(config)
@@ -212,9 +225,7 @@ class MPERunner(Runner):
         elif getattr(self.envs, "consumes_actions", True) and getattr(self.envs, "accepts_index_actions", False):
             actions_env = actions
         elif getattr(self.envs, "consumes_actions", True):      # synthetic envs ignore the actions: skip the one-hot
-            if self._onehot is None:
-                self._onehot = torch.eye(self.envs.action_space[0].n, device=b.device)
-            actions_env = self._onehot[actions.view(b.n_rollout_threads, b.num_agents).long()]   # np.eye(n)[actions]
+            actions_env = self._device_onehot(actions)
             if not env_takes_device_actions(self.envs):
                 actions_env = self._host_actions(actions_env)
         return b.value_preds[step], actions, b.action_log_probs[step], rnn_states, rnn_states_critic, actions_env
@@ -231,10 +242,20 @@ class MPERunner(Runner):
             return self._staging.download("actions_env", actions_env)
         return _t2n(actions_env)
 
+    def _device_onehot(self, actions):
+        space = self.envs.action_space[0]
+        if space.__class__.__name__ == "MultiDiscrete":
+            return onehot_actions(actions, space)
+        if self._onehot is None:
+            self._onehot = torch.eye(space.n, device=self.buffer.device)
+        return onehot_actions(actions, space, self._onehot)               # np.eye(n)[actions]
+
     def _host_onehot(self, actions):
         """One-hot env actions for a CPU env (mpe_runner.py:119, `np.eye(n)[actions]`): the integer actions come down through
         pinned memory (N x M floats instead of N x M x n) and the one-hot is built on the host, as the reference builds it."""
         b = self.buffer
+        if self.envs.action_space[0].__class__.__name__ == "MultiDiscrete":
+            return self._staging.download("actions_env", self._device_onehot(actions))
         a = self._staging.download("actions", actions.view(b.n_rollout_threads, b.num_agents))
         if self._eye_np is None:
             self._eye_np = np.eye(self.envs.action_space[0].n, dtype=np.float32)
@@ -249,9 +270,7 @@ class MPERunner(Runner):
             return self._host_onehot(actions)
         if getattr(self.envs, "accepts_index_actions", False):   # device env that decodes the buffer's action indices itself
             return actions
-        if self._onehot is None:
-            self._onehot = torch.eye(self.envs.action_space[0].n, device=b.device)
-        actions_env = self._onehot[actions.view(b.n_rollout_threads, b.num_agents).long()]       # np.eye(n)[actions]
+        actions_env = self._device_onehot(actions)
         if not env_takes_device_actions(self.envs):
             actions_env = self._host_actions(actions_env)
         return actions_env
@@ -285,11 +304,12 @@ class MPERunner(Runner):
         R = N * self.num_agents
         rnn_states = torch.zeros(R, self.recurrent_N, self.hidden_size, device=self.device)
         masks = torch.ones(R, 1, device=self.device)
-        eye = torch.eye(envs.action_space[0].n, device=self.device)
+        space = envs.action_space[0]
+        eye = torch.eye(space.n, device=self.device) if space.__class__.__name__ == "Discrete" else None
         for _ in range(self.episode_length):
             self.trainer.prep_rollout()
             action, rnn_states = self.trainer.policy.act(obs.reshape(R, -1), rnn_states, masks, deterministic=True)
-            actions_env = eye[action.view(N, self.num_agents)]
+            actions_env = onehot_actions(action.view(N, self.num_agents, -1), space, eye)
             if not env_takes_device_actions(envs):
                 actions_env = _t2n(actions_env)
             obs, rewards, dones, _ = envs.step(actions_env)

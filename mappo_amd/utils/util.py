@@ -16,6 +16,24 @@ class Discrete:
         return f"Discrete({self.n})"
 
 
+class MultiDiscrete:
+    """Stand-in for the reference's MultiDiscrete (onpolicy/envs/mpe/multi_discrete.py, matched by class name): K sub-actions,
+    sub-action j an integer in [low[j], high[j]].  `shape` is K, as the reference's buffers and policies read it."""
+
+    def __init__(self, array_of_param_array):
+        arr = np.asarray(array_of_param_array, dtype=np.int64).reshape(-1, 2)
+        self.low = arr[:, 0].copy()
+        self.high = arr[:, 1].copy()
+        if (self.high < self.low).any():
+            raise ValueError(f"MultiDiscrete: high < low in {array_of_param_array}")
+        self.num_discrete_space = int(self.low.shape[0])
+        self.n = int((self.high - self.low + 1).sum())
+        self.shape = self.num_discrete_space
+
+    def __repr__(self):
+        return "MultiDiscrete(" + str([[int(l), int(h)] for l, h in zip(self.low, self.high)]) + ")"
+
+
 def check(x):
     """onpolicy/algorithms/utils/util.py:15-17."""
     return torch.from_numpy(x) if isinstance(x, np.ndarray) else x
@@ -34,9 +52,21 @@ def get_shape_from_act_space(act_space):
     name = act_space.__class__.__name__
     if name == "Discrete":
         return 1
-    if name in ("MultiDiscrete", "Box", "MultiBinary"):
-        raise NotImplementedError(f"{name} action spaces are outside this build (BASELINE configs are all Discrete; "
+    if name == "MultiDiscrete":
+        return int(act_space.shape)
+    if name in ("Box", "MultiBinary"):
+        raise NotImplementedError(f"{name} action spaces are outside this build (BASELINE configs are Discrete / MultiDiscrete; "
                                   "Box / MultiBinary are broken in the reference itself, SURVEY.md §8c)")
+    raise NotImplementedError(name)
+
+
+def head_dims_of(act_space):
+    """Sizes of the policy's Categorical heads: (n,) for Discrete(n), (high_j - low_j + 1, ...) for MultiDiscrete (act.py:27-33)."""
+    name = act_space.__class__.__name__
+    if name == "Discrete":
+        return (int(act_space.n),)
+    if name == "MultiDiscrete":
+        return tuple(int(h) - int(l) + 1 for l, h in zip(act_space.low, act_space.high))
     raise NotImplementedError(name)
 
 
