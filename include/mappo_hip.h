@@ -480,6 +480,47 @@ int mappo_rollout_episode_spread(const float *actor_params, const mappo_net_desc
                                  float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/, float *values /*[T][B]*/,
                                  float *next_values /*[B]*/, int32_t centralized, mappo_stream_t stream);
 
+/* GPU-vectorised MPE simple_reference (csrc/mpe_ref_env.hip, device functions in csrc/mpe_ref_core.h): N environments of
+ * the scenario's fixed shape — 2 agents, 3 landmarks, dim_c = 10, action space MultiDiscrete([[0, 4], [0, 9]]) — one launch per step.
+ * Replaces MultiAgentEnv.step / _set_action (environment.py:117-256, MultiDiscrete split :198-205), World.step (core.py:207-287; the
+ * agents do not collide), Scenario.reset_world / reward / observation (scenarios/simple_reference.py:34-97) + the vec-env's
+ * reset-on-done (env_wrappers.py:146-152).  State is caller-owned device memory: agent_pos / agent_vel [N][2][2] and landmark_pos
+ * [N][3][2] in float64, goal [N][2] int32 (the landmark index of each agent's goal_b), tstep [N] int32, episode [N] int64 (reset
+ * counter = Philox counter).  The communication state is not stored: the step that sets it writes it into the observations.
+ * Outputs: obs [N][2][21] fp32 = [vel (2), landmarks - pos (6), colour of the own goal landmark (3), the other agent's c (10)],
+ * rewards [N][2] fp32 (both agents receive r_0 + r_1, r_i = -|pos(other agent) - landmark[goal_i]|^2), dones [N][2] bool bytes.
+ * action_mode 0: actions = the reference's actions_env [N][2][15] (move one-hot / probabilities [5], then c [10] taken verbatim);
+ * 1: head indices [N][2][2] as fp32 (the buffer's own K-wide action columns; move 1/2/3/4 = +x/-x/+y/-y, c = one-hot of the second).
+ * Physics in float64 with contraction off: obs and rewards EQUAL the fp32 cast of the reference's float64 values.  An environment
+ * whose episode ends (tstep >= episode_length) is reset inside the same launch and returns the reset observation (c = 0).
+ * Reset draws: Philox stream (seed, episode), 64-bit uniform number 16 n + k of environment n — k = 2 i, 2 i + 1: position of agent
+ * i in U(-1,1); k = 4 + 2 l, 5 + 2 l: position of landmark l in 0.8 U(-1,1); k = 10 + i: goal of agent i = min(2, floor(3 u)),
+ * u in [0,1); k = 12..15 unused.  Both validate on the host and name the fault: N >= 1, non-null pointers, action_mode 0 or 1,
+ * episode_length >= 1. */
+int mappo_mpe_reference_reset(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *goal, int32_t *tstep,
+                              int64_t *episode, float *obs, int32_t N, uint64_t seed, mappo_stream_t stream);
+int mappo_mpe_reference_step(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *goal, int32_t *tstep,
+                             int64_t *episode, const float *actions, int32_t action_mode, float *obs, float *rewards, uint8_t *dones,
+                             int32_t N, int32_t episode_length, uint64_t seed, mappo_stream_t stream);
+/* One launch per rollout EPISODE on the environment above, env steps included (csrc/rollout_reference.h): what T x
+ * (mappo_rollout_step_md + mappo_mpe_reference_step with action_mode 1) + the bootstrap mappo_rollout_step do, bit for bit.
+ * Per step t < T: actor on the observation rows of step t (step 0: obs_buf slot 0), head k of row i = 2 n + m sampled with counter
+ * + t (+ *counter_dev) and Philox index (k << 32) | i -> actions / logp [T][B][2]; the environments step in float64 on the sampled
+ * indices (reset-on-done after env_episode_length steps); obs -> obs_buf / share_buf slot t + 1, rewards -> rew_buf [T][B] slot t,
+ * 1 - done -> mask_buf [T+1][B] slot t + 1.  Critic on the share rows of step t <= T -> values [T][B], step T -> next_values [B].
+ * The six state arrays are stored back at the end, so the environment continues in either path.  B = 2 N rows.  Host checks, each
+ * named in the error: head_dims exactly (5, 10); actor in_dim 21, out_dim 15; both networks in_dim <= 64; the limits of the
+ * mappo_*_md entry points (layer_N <= 1, not recurrent); critic in_dim 42 (centralized) or 21, out_dim 1; same layer_N and
+ * activation; T, N, env_episode_length >= 1; non-null pointers. */
+int mappo_rollout_episode_reference(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *critic_params,
+                                    const mappo_net_desc *critic_desc /*host*/, const int32_t *head_dims /*host [n_heads]*/,
+                                    int32_t n_heads, int32_t T, int32_t N, int32_t env_episode_length, uint64_t env_seed,
+                                    double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *goal, int32_t *tstep,
+                                    int64_t *episode, int32_t deterministic, uint64_t seed, uint64_t counter,
+                                    const uint64_t *counter_dev, float *obs_buf, float *share_buf, float *rew_buf, float *mask_buf,
+                                    float *actions /*[T][B][2]*/, float *logp /*[T][B][2]*/, float *values /*[T][B]*/,
+                                    float *next_values /*[B]*/, int32_t centralized, mappo_stream_t stream);
+
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only
  * produces data of the SMAC shapes with agents that die and episodes that end.  obs [N][M][D], share_obs [N][M][S] ~ N(0,1);

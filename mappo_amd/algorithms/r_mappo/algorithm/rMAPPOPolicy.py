@@ -246,6 +246,32 @@ class R_MAPPOPolicy:
                                    b.actions, b.action_log_probs, b.value_preds, next_values, centralized)
         return next_values
 
+    def can_fuse_episode_reference(self):
+        """mappo_rollout_episode_reference: the MultiDiscrete (5, 10) policy of MPE simple_reference — 21 observation features, a
+        critic on 42 (centralized) or 21, what the stepwise MultiDiscrete launch covers (narrow, layer_N <= 1, not recurrent)."""
+        a, c = self.actor.desc, self.critic.desc
+        return (self.can_fuse_step() and tuple(self.actor.head_dims or ()) == (5, 10) and a.in_dim == 21 and c.in_dim in (21, 42)
+                and a.layer_N <= 1)
+
+    @torch.no_grad()
+    def collect_episode_reference_fused(self, buffer, env_state, next_values, centralized=True, deterministic=False):
+        """A whole rollout episode on the GPU-resident simple_reference env in one launch, env steps included
+        (mappo_rollout_episode_reference): `env_state` = SimpleReferenceVecEnv.episode_state_reference().  Writes what T x
+        (collect_step_fused + env.step) + the bootstrap call write — buffer.{actions, action_log_probs}[0..T-1] (two columns per
+        row), value_preds[0..T-1], obs / share_obs / masks [1..T], rewards [0..T-1], the critic of step T into `next_values` [N*2] —
+        and leaves the env's state where T steps leave it.  Step t samples with counter t + *_counter_dev, as the stepwise path does."""
+        b, st = buffer, env_state
+        T, N, M = b.episode_length, b.n_rollout_threads, b.num_agents
+        if st.get("scenario") != "simple_reference" or (st["N"], st["M"]) != (N, M) or st["agent_pos"].device != self.device:
+            raise ValueError("collect_episode_reference_fused: the env does not match the buffer (scenario / threads / agents / device)")
+        if not all(t.is_contiguous() for t in (b.obs, b.share_obs, b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds)):
+            raise ValueError("collect_episode_reference_fused: the buffer does not have the device layout mappo_rollout_episode_reference writes")
+        ops.rollout_episode_reference(self.actor.flat, self.actor.desc, self.critic.flat, self.critic.desc, self.actor.head_dims, T, N, st["T"],
+                                      st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"], st["goal"], st["tstep"],
+                                      st["episode"], deterministic, self.actor._seed, 0, self.actor._counter_dev, b.obs, b.share_obs,
+                                      b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds, next_values, centralized)
+        return next_values
+
     # ---- recurrent policies, SMAC-style envs: insert of the previous env output + this step's get_actions in one launch ----
     def can_fuse_recurrent_step(self, n_rows):
         from mappo_amd import recurrent

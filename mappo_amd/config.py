@@ -100,7 +100,9 @@ def get_config():
                    help="by default, with an env that hands out a whole episode up front (SyntheticMPEEnv.episode_block) and a "
                         "narrow MLP policy, the rollout episode (T x get_actions, T + 1 x get_values, every insert) is ONE kernel "
                         "launch (mappo_rollout_episode); with the GPU-resident simple_spread env (SimpleSpreadVecEnv.episode_state) the env "
-                        "steps run inside that launch too (mappo_rollout_episode_spread); pass the flag to run the stepwise loop")
+                        "steps run inside that launch too (mappo_rollout_episode_spread), and so they do with the GPU-resident simple_reference env "
+                        "and its MultiDiscrete (5, 10) policy (SimpleReferenceVecEnv, mappo_rollout_episode_reference); pass the flag to run "
+                        "the stepwise loop")
     p.add_argument("--dual_update", **off,
                    help="by default the actor's and the critic's fused update run in ONE launch, half the CUs each "
                         "(mappo_actor_critic_update); pass the flag to launch them one after the other")

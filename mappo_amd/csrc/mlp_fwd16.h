@@ -173,8 +173,9 @@ __device__ __forceinline__ void head16r_load(Head16R<MODE> &hd, const float *P, 
 // results do not depend on which launch computes them.  DRAIN (episode kernel): wait for every load in flight — the next step's
 // rows, requested before this step's math — in front of the stores.  The stores sit in a divergent branch, so behind them the
 // counter can only be drained whole: the next step's wait for its rows would also wait for this step's stores to complete.
-// ACT_TILE (MODE 1, the episode kernel that steps its environments itself): the action of tile row j also goes to act_tile[j]
-// in LDS, where the wave's environment lanes pick it up behind the closing wave_lds_sync.  TW / HD: where the weights come from
+// ACT_TILE (the episode kernels that step their environments themselves): the action of tile row j also goes to act_tile[j]
+// (MODE 1) / the row's K head actions to act_tile[j][K] (MODE 5) in LDS, where the environment lanes pick them up behind the
+// closing wave_lds_sync.  TW / HD: where the weights come from
 // (Trunk16R / Head16R: registers; Trunk16L / Head16L: LDS) — same operands, same order, same arithmetic.
 // MODE 5 (MultiDiscrete): MODE 1 with the multi-head epilogue — the row's lane walks the heads of `md` over its logits row and
 // writes actions / logp [i][md->n]; block 0 of the head is computed exactly as in MODE 1, so one head reproduces Discrete.
@@ -227,7 +228,12 @@ __device__ __forceinline__ void tile16r_step(const FwdArgs &p, const TW &tw, con
       if constexpr (MODE == 5) {
         if (ok && q == 0) {
           const uint64_t ctr = ctr_base + (ctr_dev ? *ctr_dev : 0ull);
-          categorical_act_heads(tZ + j * TP, *md, p.deterministic != 0, p.seed, ctr, (uint64_t)i, actions + i * md->n, logp + i * md->n);
+          if constexpr (ACT_TILE) {                                             // the row's K actions go to act_tile[j][K], and from there to the buffer
+            categorical_act_heads(tZ + j * TP, *md, p.deterministic != 0, p.seed, ctr, (uint64_t)i, act_tile + j * md->n, logp + i * md->n);
+            for (int k = 0; k < md->n; ++k) actions[i * md->n + k] = act_tile[j * md->n + k];
+          } else {
+            categorical_act_heads(tZ + j * TP, *md, p.deterministic != 0, p.seed, ctr, (uint64_t)i, actions + i * md->n, logp + i * md->n);
+          }
         }
       } else if (ok && q == 0) {
         const uint64_t ctr = ctr_base + (ctr_dev ? *ctr_dev : 0ull);

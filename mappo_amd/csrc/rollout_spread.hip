@@ -1,3 +1,5 @@
-// rollout_spread.hip — the one-launch rollout episode on the GPU-resident simple_spread environment (see rollout_spread.h)
+// rollout_spread.hip — the one-launch rollout episodes on the GPU-resident environments: simple_spread (see rollout_spread.h) and
+// simple_reference (see rollout_reference.h)
 #include "mlp_host.h"
 #include "rollout_spread.h"
+#include "rollout_reference.h"

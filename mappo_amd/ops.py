@@ -368,6 +368,26 @@ def rollout_episode_spread(actor_params, actor_desc, critic_params, critic_desc,
     _lib.check(rc, "mappo_rollout_episode_spread")
 
 
+def rollout_episode_reference(actor_params, actor_desc, critic_params, critic_desc, head_dims, T, N, env_episode_length, env_seed,
+                              agent_pos, agent_vel, landmark_pos, goal, tstep, episode, deterministic, seed, counter, counter_dev, obs_buf,
+                              share_buf, rew_buf, mask_buf, actions, logp, values, next_values, centralized):
+    """A whole rollout episode on the GPU-resident simple_reference env in one launch, env steps included
+    (mappo_rollout_episode_reference): the six env state tensors (SimpleReferenceVecEnv) are read, stepped T times on the sampled
+    head indices and stored back; the buffer arrays are the contiguous SharedReplayBuffer tensors (actions / action_log_probs
+    [T, N, 2, 2]).  head_dims must be (5, 10)."""
+    f64 = torch.float64
+    arr, K = _heads(head_dims)
+    rc = _lib.load().mappo_rollout_episode_reference(_ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), arr, K,
+                                                     int(T), int(N), int(env_episode_length), int(env_seed) & (2 ** 64 - 1),
+                                                     _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
+                                                     _ptr(goal, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64),
+                                                     int(bool(deterministic)), int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
+                                                     _ptr(counter_dev, torch.int64, allow_none=True), _ptr(obs_buf), _ptr(share_buf),
+                                                     _ptr(rew_buf), _ptr(mask_buf), _ptr(actions), _ptr(logp), _ptr(values), _ptr(next_values),
+                                                     int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode_reference")
+
+
 def mlp_backward_slabs(B):
     return int(_lib.load().mappo_mlp_backward_slabs(int(B)))
 
@@ -651,6 +671,26 @@ def mpe_spread_step(agent_pos, agent_vel, landmark_pos, tstep, episode, actions,
                                            _ptr(dones, torch.uint8), int(N), int(M), int(L),
                                            int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
     _lib.check(rc, "mappo_mpe_spread_step")
+
+
+# ---- GPU-vectorised MPE simple_reference (csrc/mpe_ref_env.hip): 2 agents, 3 landmarks, MultiDiscrete (5, 10) ----------------
+def mpe_reference_reset(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, obs, N, seed):
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_reference_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                               _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs), int(N),
+                                               int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_reference_reset")
+
+
+def mpe_reference_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, actions, action_mode, obs, rewards, dones, N,
+                       episode_length, seed):
+    """action_mode 0: actions [N, 2, 15] (the heads' one-hots side by side) | 1: [N, 2, 2] fp32 head indices."""
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_reference_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                              _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(actions), int(action_mode),
+                                              _ptr(obs), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length),
+                                              int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_reference_step")
 
 
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):

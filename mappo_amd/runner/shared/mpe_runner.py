@@ -103,6 +103,18 @@ class MPERunner(Runner):
             self.trainer.prep_rollout()
             b.compute_returns(nv, self.trainer.value_normalizer)
             return infos
+        if fuse and self._fuse_episode and self._episode_reference_env() and self.trainer.policy.can_fuse_episode_reference():
+            # simple_reference on the device with its MultiDiscrete (5, 10) policy: the episode, env steps included, is ONE launch
+            # (mappo_rollout_episode_reference), same buffer contents and env state as the stepwise loop below
+            b = self.buffer
+            if self._next_values is None:
+                self._next_values = torch.empty(b.n_rollout_threads * b.num_agents, device=b.device)
+            nv = self.trainer.policy.collect_episode_reference_fused(b, self.envs.episode_state_reference(), self._next_values,
+                                                                     self.use_centralized_V)
+            b.step = 0
+            self.trainer.prep_rollout()
+            b.compute_returns(nv, self.trainer.value_normalizer)
+            return infos
         pending = None                     # env output of the previous step, not yet in the buffer (fused path)
         for step in range(self.episode_length):
             if fuse:
@@ -169,6 +181,18 @@ class MPERunner(Runner):
             dev = torch.device("cuda", torch.cuda.current_device())
         a = self.trainer.policy.actor.desc
         return dev == self.trainer.policy.device and a.in_dim == env.obs_dim and a.out_dim == 5
+
+    def _episode_reference_env(self):
+        """The env is SimpleReferenceVecEnv (it steps inside mappo_rollout_episode_reference) with its state on the policy's device
+        and no host staging in between."""
+        from mappo_amd.envs.mpe_reference import SimpleReferenceVecEnv
+        env = self.envs
+        if not isinstance(env, SimpleReferenceVecEnv) or self._staging is not None:
+            return False
+        dev = torch.device(env.device)
+        if dev.type == "cuda" and dev.index is None:            # where its tensors land
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return dev == self.trainer.policy.device and env.M == self.num_agents
 
     def rollout(self):
         """T x (collect, env.step, insert) + compute().  With a vec-env that declares `graph_safe` (device-resident,
