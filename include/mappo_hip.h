@@ -521,6 +521,59 @@ int mappo_rollout_episode_reference(const float *actor_params, const mappo_net_d
                                     float *actions /*[T][B][2]*/, float *logp /*[T][B][2]*/, float *values /*[T][B]*/,
                                     float *next_values /*[B]*/, int32_t centralized, mappo_stream_t stream);
 
+/* GPU-vectorised MPE simple_speaker_listener (csrc/mpe_comm_env.hip, device functions in csrc/mpe_comm_core.h): N environments of the
+ * scenario's fixed shape — agent 0 the SPEAKER (does not move; observes the goal landmark's colour, 3 features; Discrete(3): the
+ * symbol it says), agent 1 the LISTENER (silent; observes velocity 2, the 3 landmarks relative to itself 6, the speaker's symbol 3 =
+ * 11 features; Discrete(5)), 3 landmarks — one launch per step.  Replaces MultiAgentEnv.step / _set_action (environment.py:117-256),
+ * World.step (core.py:207-287; nothing collides), Scenario.reset_world / reward / observation
+ * (scenarios/simple_speaker_listener.py:38-98) + the vec-env's reset-on-done (env_wrappers.py:146-152).  State is caller-owned device
+ * memory: listener_pos / listener_vel [N][2] and landmark_pos [N][3][2] in float64, goal [N] int32 (the landmark index of the
+ * speaker's goal_b), symbol [N] int32 (what the channel holds: 0..2, or -1 for none after a reset), tstep [N] int32, episode [N]
+ * int64 (reset counter = Philox counter).  The speaker's own position and velocity are neither observed nor rewarded and are not
+ * kept.  Outputs: obs_speaker [N][3], obs_listener [N][11] fp32 (the listener hears the symbol said in the same step; zeros after a
+ * reset), rewards [N][2] fp32 (collaborative: both agents receive the sum over the agents, 2 x -|listener - goal landmark|^2), dones
+ * [N][2] bool bytes.  action_mode 0: the reference's one-hots / probabilities, actions_speaker [N][3] (taken verbatim as c) and
+ * actions_listener [N][5]; 1: indices as fp32, actions_speaker = [N][2] (symbol, move; a symbol outside 0..2 is clamped, in the state and in the observation alike), actions_listener unused (may be NULL; move
+ * 1/2/3/4 = +x/-x/+y/-y).  Physics in float64 with contraction off: obs and rewards EQUAL the fp32 cast of the reference's float64
+ * values.  An environment whose episode ends (tstep >= episode_length) is reset inside the same launch and returns the reset
+ * observation.  Reset draws: Philox stream (seed, episode), 64-bit uniform number 16 n + k of environment n — k = 0, 1: listener
+ * position in U(-1,1); k = 2 + 2 l, 3 + 2 l: position of landmark l in U(-1,1); k = 8: goal = min(2, floor(3 u)), u in [0,1);
+ * k = 9..15 unused.  Both validate on the host and name the fault: N >= 1, non-null pointers, action_mode 0 or 1,
+ * episode_length >= 1. */
+int mappo_mpe_comm_reset(double *listener_pos, double *listener_vel, double *landmark_pos, int32_t *goal, int32_t *symbol,
+                         int32_t *tstep, int64_t *episode, float *obs_speaker, float *obs_listener, int32_t N, uint64_t seed,
+                         mappo_stream_t stream);
+int mappo_mpe_comm_step(double *listener_pos, double *listener_vel, double *landmark_pos, int32_t *goal, int32_t *symbol,
+                        int32_t *tstep, int64_t *episode, const float *actions_speaker, const float *actions_listener,
+                        int32_t action_mode, float *obs_speaker, float *obs_listener, float *rewards, uint8_t *dones, int32_t N,
+                        int32_t episode_length, uint64_t seed, mappo_stream_t stream);
+/* One agent of the launch below: its two networks, its sampling seed and counter word and the arrays of its SeparatedReplayBuffer (contiguous;
+ * rows = environments): obs_buf [T+1][N][D_m], share_buf [T+1][N][S_m], rew_buf [T][N], mask_buf [T+1][N], actions / logp / values
+ * [T][N] (values: slots 0..T-1 of value_preds), next_values [N]. */
+typedef struct mappo_comm_agent {
+  const float *actor_params, *critic_params;
+  mappo_net_desc actor_desc, critic_desc;
+  uint64_t seed;
+  const uint64_t *counter_dev;   /* device word added to `counter` for this agent's draws, or NULL */
+  float *obs_buf, *share_buf, *rew_buf, *mask_buf, *actions, *logp, *values, *next_values;
+} mappo_comm_agent;
+/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner (csrc/rollout_comm.h): what
+ * T x (one mappo_rollout_step per agent + mappo_mpe_comm_step with action_mode 1 + the agents' inserts) + one bootstrap
+ * mappo_rollout_step per agent do, bit for bit.  Per step t < T: agent m's actor on its observation rows of step t (step 0: obs_buf
+ * slot 0), row n sampled with (agent's seed, counter + t (+ the agent's *counter_dev), Philox index n) -> actions / logp slot t; the environments
+ * step in float64 on the sampled indices (reset-on-done after env_episode_length steps); each agent's observation -> its obs_buf
+ * slot t + 1, its share row (centralized: speaker's 3 then listener's 11 = 14; else its own observation) -> share_buf slot t + 1,
+ * the shared reward -> rew_buf slot t, 1 - done -> mask_buf slot t + 1.  Each critic on its share rows of step t <= T -> values,
+ * step T -> next_values.  The seven state arrays are stored back at the end, so the environment continues in either path.  Host
+ * checks, each named in the error: non-null descriptors; not recurrent; layer_N <= 1; speaker actor in 3 / out 3, listener actor in
+ * 11 / out 5; critics out 1 and in 14 (centralized) or the agent's own in_dim; the same layer_N and activation in all four
+ * networks; T, N, env_episode_length >= 1; non-null pointers. */
+int mappo_rollout_episode_comm(const mappo_comm_agent *speaker /*host*/, const mappo_comm_agent *listener /*host*/, int32_t T,
+                               int32_t N, int32_t env_episode_length, uint64_t env_seed, double *listener_pos, double *listener_vel,
+                               double *landmark_pos, int32_t *goal, int32_t *symbol, int32_t *tstep, int64_t *episode,
+                               int32_t deterministic, uint64_t counter, int32_t centralized,
+                               mappo_stream_t stream);
+
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only
  * produces data of the SMAC shapes with agents that die and episodes that end.  obs [N][M][D], share_obs [N][M][S] ~ N(0,1);

@@ -32,6 +32,13 @@ class SmacSlot(C.Structure):
                                           "rnn_states", "rnn_states_critic")]
 
 
+class CommAgent(C.Structure):
+    """mappo_comm_agent: one agent of mappo_rollout_episode_comm — networks, sampling seed, buffer arrays (include/mappo_hip.h)."""
+    _fields_ = ([("actor_params", C.c_void_p), ("critic_params", C.c_void_p), ("actor_desc", NetDesc), ("critic_desc", NetDesc),
+                 ("seed", C.c_uint64), ("counter_dev", C.c_void_p)] +
+                [(n, C.c_void_p) for n in ("obs_buf", "share_buf", "rew_buf", "mask_buf", "actions", "logp", "values", "next_values")])
+
+
 _P, _I32, _I64, _F, _D, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint64
 
 # name -> (restype, argtypes); must list every symbol include/mappo_hip.h declares (tests/test_capi_symbols.py)
@@ -119,6 +126,10 @@ SIGNATURES = {
     "mappo_mpe_reference_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _U64, _P]),
     "mappo_rollout_episode_reference": (C.c_int, [_P, C.POINTER(NetDesc), _P, C.POINTER(NetDesc), C.POINTER(_I32), _I32, _I32, _I32, _I32, _U64,
                                                   _P, _P, _P, _P, _P, _P, _I32, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "mappo_mpe_comm_reset": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _U64, _P]),
+    "mappo_mpe_comm_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _U64, _P]),
+    "mappo_rollout_episode_comm": (C.c_int, [C.POINTER(CommAgent), C.POINTER(CommAgent), _I32, _I32, _I32, _U64, _P, _P, _P, _P, _P, _P, _P,
+                                             _I32, _U64, _I32, _P]),
     "mappo_profile_arm": (C.c_int, [_I32, _P, _P]),
     "mappo_selftest_mfma": (C.c_int, [_P, _P, _P, _P]),
 }

@@ -12,7 +12,7 @@ void mappo_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *mappo_last_error(void) { return g_err; }
-extern "C" int mappo_abi_version(void) { return 5; }   // 4: the MultiDiscrete entry points (mappo_*_md); 5: simple_reference (mappo_mpe_reference_*, mappo_rollout_episode_reference)
+extern "C" int mappo_abi_version(void) { return 6; }   // 4: the MultiDiscrete entry points (mappo_*_md); 5: simple_reference (mappo_mpe_reference_*, mappo_rollout_episode_reference); 6: simple_speaker_listener (mappo_mpe_comm_*, mappo_rollout_episode_comm)
 
 ProfSlot g_prof[MAPPO_PROF_COUNT] = {};
 

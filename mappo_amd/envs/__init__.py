@@ -1,0 +1,1 @@
+from .mpe_speaker_listener import SimpleSpeakerListenerVecEnv  # noqa: F401

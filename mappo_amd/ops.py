@@ -388,6 +388,36 @@ def rollout_episode_reference(actor_params, actor_desc, critic_params, critic_de
     _lib.check(rc, "mappo_rollout_episode_reference")
 
 
+def comm_agent(actor_params, actor_desc, critic_params, critic_desc, seed, counter_dev, obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values,
+               next_values):
+    """One agent of rollout_episode_comm (mappo_comm_agent): its networks, its sampling seed and counter word (int64 [1] device tensor or None) and the contiguous arrays of its
+    SeparatedReplayBuffer."""
+    ag = _lib.CommAgent()
+    ag.actor_params, ag.critic_params = _ptr(actor_params).value, _ptr(critic_params).value
+    ag.actor_desc, ag.critic_desc = actor_desc, critic_desc
+    ag.seed = int(seed) & (2 ** 64 - 1)
+    cd = _ptr(counter_dev, torch.int64, allow_none=True)
+    ag.counter_dev = cd.value if cd is not None else None
+    for name, t in (("obs_buf", obs_buf), ("share_buf", share_buf), ("rew_buf", rew_buf), ("mask_buf", mask_buf), ("actions", actions),
+                    ("logp", logp), ("values", values), ("next_values", next_values)):
+        setattr(ag, name, _ptr(t).value)
+    return ag
+
+
+def rollout_episode_comm(speaker, listener, T, N, env_episode_length, env_seed, listener_pos, listener_vel, landmark_pos, goal, symbol,
+                         tstep, episode, deterministic, counter, centralized):
+    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_speaker_listener env in one launch, env steps
+    included (mappo_rollout_episode_comm).  speaker / listener: comm_agent(...) of agent 0 / 1; the seven env state tensors
+    (SimpleSpeakerListenerVecEnv) are read, stepped T times on the sampled indices and stored back."""
+    f64 = torch.float64
+    rc = _lib.load().mappo_rollout_episode_comm(C.byref(speaker), C.byref(listener), int(T), int(N), int(env_episode_length),
+                                                int(env_seed) & (2 ** 64 - 1), _ptr(listener_pos, f64), _ptr(listener_vel, f64),
+                                                _ptr(landmark_pos, f64), _ptr(goal, torch.int32), _ptr(symbol, torch.int32),
+                                                _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(bool(deterministic)),
+                                                int(counter) & (2 ** 64 - 1), int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode_comm")
+
+
 def mlp_backward_slabs(B):
     return int(_lib.load().mappo_mlp_backward_slabs(int(B)))
 
@@ -691,6 +721,28 @@ def mpe_reference_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
                                               _ptr(obs), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length),
                                               int(seed) & (2 ** 64 - 1), _stream())
     _lib.check(rc, "mappo_mpe_reference_step")
+
+
+# ---- GPU-vectorised MPE simple_speaker_listener (csrc/mpe_comm_env.hip): speaker Discrete(3), listener Discrete(5) -----------------
+def mpe_comm_reset(listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode, obs_speaker, obs_listener, N, seed):
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_comm_reset(_ptr(listener_pos, f64), _ptr(listener_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                          _ptr(symbol, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs_speaker),
+                                          _ptr(obs_listener), int(N), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_comm_reset")
+
+
+def mpe_comm_step(listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode, actions_speaker, actions_listener, action_mode,
+                  obs_speaker, obs_listener, rewards, dones, N, episode_length, seed):
+    """action_mode 0: one-hots, actions_speaker [N, 3] and actions_listener [N, 5] | 1: actions_speaker = fp32 indices [N, 2]
+    (symbol, move), actions_listener None."""
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_comm_step(_ptr(listener_pos, f64), _ptr(listener_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                         _ptr(symbol, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64),
+                                         _ptr(actions_speaker), _ptr(actions_listener, allow_none=True), int(action_mode), _ptr(obs_speaker),
+                                         _ptr(obs_listener), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length),
+                                         int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_comm_step")
 
 
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):

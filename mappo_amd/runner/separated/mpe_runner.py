@@ -3,7 +3,15 @@ trainer and SeparatedReplayBuffer; an iteration is T x (collect, env.step, inser
 
 Data stay in HBM: `collect` runs each agent's actor + critic kernels on its buffer slot (outputs land in the slot,
 R_MAPPOPolicy.collect_into), `insert` stores the agent's column of the env output.  The share_obs of an agent under
-use_centralized_V is the concatenation of all agents' observations of the thread (separated/mpe_runner.py:84-96,160-166)."""
+use_centralized_V is the concatenation of all agents' observations of the thread (separated/mpe_runner.py:84-96,160-166).
+
+Agents may differ in shape (MPE simple_speaker_listener: observations of 3 and 11 features, Discrete(3) and Discrete(5)): the env's
+observations are then a list of per-agent tensors (mappo_amd.envs.mpe_speaker_listener) or the reference's host form, an object
+array [N, M] of per-agent arrays; one-hot widths come from each agent's own action space.  On such an env feed-forward policies
+collect through mappo_rollout_step (one launch per agent for actor + critic), and on the GPU-resident speaker-listener env the
+whole episode — both agents' networks, the env steps and the inserts — is ONE launch (mappo_rollout_episode_comm) with the same
+buffer contents and env state, bit for bit; MAPPO_COMM_EPISODE=0 keeps the stepwise path (A/B runs, tests)."""
+import os
 import time
 
 import numpy as np
@@ -16,6 +24,12 @@ class MPERunner(Runner):
     def __init__(self, config):
         super().__init__(config)
         self._eye = None
+        obs_dims = [self.buffer[m].obs.shape[-1] for m in range(self.num_agents)]
+        act_dims = [self.envs.action_space[m].n for m in range(self.num_agents)]
+        # agents of different shapes: per-agent observation lists, per-agent one-hot widths
+        self._ragged = bool(getattr(self.envs, "ragged_obs", False)) or len(set(obs_dims)) > 1 or len(set(act_dims)) > 1
+        self._eyes = {}
+        self._next_values = None
 
     def run(self):
         self.warmup()
@@ -42,13 +56,26 @@ class MPERunner(Runner):
         if self.use_linear_lr_decay:
             for agent_id in range(self.num_agents):
                 self.trainer[agent_id].policy.lr_decay(episode, episodes)
+        infos = self.rollout()
+        return self.train(), infos
+
+    def rollout(self, deterministic=False):
+        """T x (collect, env.step, insert) + compute() — as one launch where the env and the policies allow it."""
         infos = None
+        if self._ragged:
+            # a fresh sampling stream per episode, as the shared runner's rollout: step t of this episode draws with counter
+            # t + *_counter_dev, every agent from its own word
+            for p in self.policy:
+                p.actor._counter_dev.add_(self.episode_length)
+        if self._comm_episode_ready():
+            self._collect_episode_comm(deterministic)
+            return infos
         for step in range(self.episode_length):
-            values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env = self.collect(step)
+            values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env = self.collect(step, deterministic)
             obs, rewards, dones, infos = self.envs.step(actions_env)
             self.insert((obs, rewards, dones, infos, values, actions, action_log_probs, rnn_states, rnn_states_critic))
         self.compute()
-        return self.train(), infos
+        return infos
 
     def _dev(self, x, dtype=torch.float32):
         if torch.is_tensor(x):
@@ -59,33 +86,130 @@ class MPERunner(Runner):
         N = obs_t.shape[0]
         return obs_t.reshape(N, -1)                                 # all agents' obs of a thread, side by side
 
+    def _obs_agents(self, obs):
+        """Env observations -> (per-agent device tensors [N, D_m], share [N, sum D_m]).  Accepted forms: a tensor / array [N, M, D];
+        a list of M per-agent tensors; the reference's host form for agents of different shapes, an object array [N, M] of
+        per-agent arrays (separated/mpe_runner.py:160-166: np.array(list(obs[:, agent_id])), share = chain(*o) per thread)."""
+        if isinstance(obs, (list, tuple)):
+            per = [self._dev(o) for o in obs]
+        elif isinstance(obs, np.ndarray) and obs.dtype == object:
+            per = [self._dev(np.array(list(obs[:, agent_id]), dtype=np.float32)) for agent_id in range(self.num_agents)]
+        else:
+            obs = self._dev(obs)
+            return [obs[:, agent_id] for agent_id in range(self.num_agents)], self._share(obs)
+        if len(per) != self.num_agents:
+            raise ValueError(f"the env returned observations of {len(per)} agents, the runner has {self.num_agents}")
+        return per, torch.cat(per, dim=1)
+
+    def _fused_ff(self):
+        """Agents of different shapes with feed-forward policies the one-launch step covers: collect and the bootstrap value go
+        through mappo_rollout_step (the arithmetic the one-launch episode reproduces bit for bit).  Homogeneous runs keep
+        collect_into."""
+        return self._ragged and all(p.can_fuse_step() and max(p.actor.desc.in_dim, p.critic.desc.in_dim) <= 64 and not p.actor.head_dims
+                                    for p in self.policy)
+
+    def _actions_env(self, envs, acts):
+        """acts: per-agent index tensors [N] -> what envs.step takes.  Same shapes: np.eye(n)[action], [N, M, n], as ever.  Different
+        shapes: indices [N, M] for an env that decodes them itself (accepts_index_actions), else a per-agent list of one-hots
+        [N, n_m] — NumPy arrays for a host env."""
+        if not self._ragged:
+            n_act = envs.action_space[0].n
+            if self._eye is None or self._eye.shape[0] != n_act:
+                self._eye = torch.eye(n_act, device=self.device)
+            actions_env = self._eye[torch.stack(acts, dim=1)]                     # np.eye(n)[action] per agent, [N, M, n]
+            return actions_env if env_takes_device_actions(envs) else _t2n(actions_env)
+        if getattr(envs, "accepts_index_actions", False) and env_takes_device_actions(envs):
+            return torch.stack(acts, dim=1).to(torch.float32)
+        out = []
+        for agent_id, a in enumerate(acts):
+            n_act = envs.action_space[agent_id].n
+            if n_act not in self._eyes:
+                self._eyes[n_act] = torch.eye(n_act, device=self.device)
+            out.append(self._eyes[n_act][a])
+        return out if env_takes_device_actions(envs) else [_t2n(x) for x in out]
+
     # separated/mpe_runner.py:81-96
     def warmup(self):
-        obs = self._dev(self.envs.reset())
-        share = self._share(obs)
+        obs, share = self._obs_agents(self.envs.reset())
         for agent_id in range(self.num_agents):
             b = self.buffer[agent_id]
-            b.share_obs[0].copy_(share if self.use_centralized_V else obs[:, agent_id])
-            b.obs[0].copy_(obs[:, agent_id])
+            b.share_obs[0].copy_(share if self.use_centralized_V else obs[agent_id])
+            b.obs[0].copy_(obs[agent_id])
+
+    # ---- one rollout episode in one launch (mappo_rollout_episode_comm) ----
+    def _comm_episode_ready(self):
+        """The env is the GPU-resident simple_speaker_listener (it steps inside the launch), both policies are what the kernel is
+        built for (feed-forward, narrow, layer_N <= 1, one layer_N and activation in all four networks, the scenario's shapes) and
+        the buffers have the device layout it writes.  Anything else takes the stepwise path."""
+        env = self.envs
+        if os.environ.get("MAPPO_COMM_EPISODE", "1") == "0" or not hasattr(env, "episode_state_comm") or self.num_agents != 2:
+            return False
+        if not self._fused_ff():
+            return False
+        dev = env.listener_pos.device                           # where its tensors landed
+        d0 = self.policy[0].actor.desc
+        S = sum(env.obs_dims)
+        for agent_id, p in enumerate(self.policy):
+            a, c, b = p.actor.desc, p.critic.desc, self.buffer[agent_id]
+            if (dev != p.flat_params.device or a.layer_N > 1 or (a.layer_N, a.use_relu) != (d0.layer_N, d0.use_relu)
+                    or (a.in_dim, a.out_dim) != (env.obs_dims[agent_id], env.act_dims[agent_id])
+                    or c.in_dim != (S if self.use_centralized_V else env.obs_dims[agent_id])
+                    or b.n_rollout_threads != env.N or b.episode_length != self.episode_length
+                    or not all(t.is_contiguous() and t.dtype == torch.float32
+                               for t in (b.obs, b.share_obs, b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds))):
+                return False
+        return True
+
+    @torch.no_grad()
+    def _collect_episode_comm(self, deterministic=False):
+        """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent."""
+        st = self.envs.episode_state_comm()
+        N = self.n_rollout_threads
+        if self._next_values is None:
+            self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
+        from mappo_amd import ops
+        ags = []
+        for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer)):
+            ags.append(ops.comm_agent(p.actor.flat, p.actor.desc, p.critic.flat, p.critic.desc, p.actor._seed, p.actor._counter_dev, b.obs, b.share_obs, b.rewards,
+                                      b.masks, b.actions, b.action_log_probs, b.value_preds, self._next_values[agent_id]))
+        ops.rollout_episode_comm(ags[0], ags[1], self.episode_length, N, st["T"], st["seed"], st["listener_pos"], st["listener_vel"],
+                                 st["landmark_pos"], st["goal"], st["symbol"], st["tstep"], st["episode"], deterministic, 0,
+                                 self.use_centralized_V)
+        for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
+            b.step = 0
+            tr.prep_rollout()
+            b.compute_returns(self._next_values[agent_id], tr.value_normalizer)
+
+    @torch.no_grad()
+    def compute(self):
+        if not self._fused_ff():
+            return super().compute()
+        # the bootstrap value through mappo_rollout_step's critic, as the stepwise collect below
+        N = self.n_rollout_threads
+        if self._next_values is None:
+            self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
+        for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
+            tr.prep_rollout()
+            nv = tr.policy.collect_step_fused(b, self.episode_length, None, self.use_centralized_V, values_only=self._next_values[agent_id])
+            b.compute_returns(nv, tr.value_normalizer)
 
     # separated/mpe_runner.py:98-151
     @torch.no_grad()
-    def collect(self, step):
+    def collect(self, step, deterministic=False):
         N = self.n_rollout_threads
         values, actions, logps, rnn_a, rnn_c = [], [], [], [], []
+        fused = self._fused_ff()
         for agent_id in range(self.num_agents):
             tr, b = self.trainer[agent_id], self.buffer[agent_id]
             tr.prep_rollout()
-            act, ra, rc = tr.policy.collect_into(b, step)           # outputs land in b.{actions, action_log_probs, value_preds}[step]
+            if fused:                                               # actor + critic of the agent in one launch, on buffer slot `step`
+                act, ra, rc = tr.policy.collect_step_fused(b, step, None, self.use_centralized_V, deterministic=deterministic), None, None
+            else:
+                act, ra, rc = tr.policy.collect_into(b, step, deterministic=deterministic)       # outputs land in b.{actions, action_log_probs, value_preds}[step]
             values.append(b.value_preds[step]); actions.append(act.view(N, 1)); logps.append(b.action_log_probs[step])
             rnn_a.append(ra); rnn_c.append(rc)
         actions = torch.stack(actions, dim=1)                       # [N, M, 1]
-        n_act = self.envs.action_space[0].n
-        if self._eye is None:
-            self._eye = torch.eye(n_act, device=self.device)
-        actions_env = self._eye[actions.view(N, self.num_agents).long()]          # np.eye(n)[action] per agent, [N, M, n]
-        if not env_takes_device_actions(self.envs):
-            actions_env = _t2n(actions_env)
+        actions_env = self._actions_env(self.envs, [actions[:, agent_id, 0].long() for agent_id in range(self.num_agents)])
         stack = lambda xs: torch.stack([x.view(N, *x.shape[1:]) if x is not None else torch.zeros(N, self.recurrent_N, self.hidden_size,
                                                                                                  device=self.device) for x in xs], dim=1)
         return torch.stack(values, dim=1), actions, torch.stack(logps, dim=1), stack(rnn_a), stack(rnn_c), actions_env
@@ -94,10 +218,9 @@ class MPERunner(Runner):
     def insert(self, data):
         obs, rewards, dones, infos, values, actions, action_log_probs, rnn_states, rnn_states_critic = data
         N = self.n_rollout_threads
-        obs, rewards = self._dev(obs), self._dev(rewards)
+        (obs, share), rewards = self._obs_agents(obs), self._dev(rewards)
         dones = self._dev(dones, torch.bool).view(N, self.num_agents)
         masks = (~dones).to(torch.float32).view(N, self.num_agents, 1)
-        share = self._share(obs)
         recurrent = self.trainer[0]._use_recurrent_policy or self.trainer[0]._use_naive_recurrent
         for agent_id in range(self.num_agents):
             b = self.buffer[agent_id]
@@ -106,7 +229,7 @@ class MPERunner(Runner):
                 keep = masks[:, agent_id].view(N, 1, 1)
                 ra = rnn_states[:, agent_id].reshape(N, self.recurrent_N, -1) * keep
                 rc = rnn_states_critic[:, agent_id].reshape(N, self.recurrent_N, -1) * keep
-            b.insert_env(share if self.use_centralized_V else obs[:, agent_id], obs[:, agent_id], rewards[:, agent_id].reshape(N, 1),
+            b.insert_env(share if self.use_centralized_V else obs[agent_id], obs[agent_id], rewards[:, agent_id].reshape(N, 1),
                          masks[:, agent_id], ra, rc)
 
     # separated/mpe_runner.py:180-236
@@ -115,25 +238,21 @@ class MPERunner(Runner):
         envs = self.eval_envs
         if envs is None:
             return
-        obs = self._dev(envs.reset())
-        N = obs.shape[0]
+        obs, _ = self._obs_agents(envs.reset())
+        N = obs[0].shape[0]
         rnn = [torch.zeros(N, self.recurrent_N, self.hidden_size, device=self.device) for _ in range(self.num_agents)]
         masks = torch.ones(N, self.num_agents, 1, device=self.device)
-        eye = torch.eye(envs.action_space[0].n, device=self.device)
         rews = []
         for _ in range(self.episode_length):
             acts = []
             for agent_id in range(self.num_agents):
                 self.trainer[agent_id].prep_rollout()
-                a, rnn[agent_id] = self.trainer[agent_id].policy.act(obs[:, agent_id], rnn[agent_id], masks[:, agent_id], deterministic=True)
+                a, rnn[agent_id] = self.trainer[agent_id].policy.act(obs[agent_id], rnn[agent_id], masks[:, agent_id], deterministic=True)
                 acts.append(a.view(N))
-            actions_env = eye[torch.stack(acts, dim=1)]
-            if not env_takes_device_actions(envs):
-                actions_env = _t2n(actions_env)
-            obs, rewards, dones, _ = envs.step(actions_env)
-            obs = self._dev(obs)
+            obs, rewards, dones, _ = envs.step(self._actions_env(envs, [a.long() for a in acts]))
+            obs, _ = self._obs_agents(obs)
             dones = self._dev(dones, torch.bool).view(N, self.num_agents)
-            rews.append(self._dev(rewards).view(N, self.num_agents))
+            rews.append(self._dev(rewards).view(N, self.num_agents).clone())    # a device env hands out recycled output tensors
             masks = (~dones).to(torch.float32).view(N, self.num_agents, 1)
             for agent_id in range(self.num_agents):
                 rnn[agent_id] = rnn[agent_id].view(N, self.recurrent_N, -1) * masks[:, agent_id].view(N, 1, 1)
