@@ -547,7 +547,7 @@ int mappo_mpe_comm_step(double *listener_pos, double *listener_vel, double *land
                         int32_t *tstep, int64_t *episode, const float *actions_speaker, const float *actions_listener,
                         int32_t action_mode, float *obs_speaker, float *obs_listener, float *rewards, uint8_t *dones, int32_t N,
                         int32_t episode_length, uint64_t seed, mappo_stream_t stream);
-/* One agent of the launch below: its two networks, its sampling seed and counter word and the arrays of its SeparatedReplayBuffer (contiguous;
+/* One agent of the separated runner's episode launches below (mappo_rollout_episode_comm, mappo_rollout_episode_adversary): its two networks, its sampling seed and counter word and the arrays of its SeparatedReplayBuffer (contiguous;
  * rows = environments): obs_buf [T+1][N][D_m], share_buf [T+1][N][S_m], rew_buf [T][N], mask_buf [T+1][N], actions / logp / values
  * [T][N] (values: slots 0..T-1 of value_preds), next_values [N]. */
 typedef struct mappo_comm_agent {
@@ -573,6 +573,50 @@ int mappo_rollout_episode_comm(const mappo_comm_agent *speaker /*host*/, const m
                                double *landmark_pos, int32_t *goal, int32_t *symbol, int32_t *tstep, int64_t *episode,
                                int32_t deterministic, uint64_t counter, int32_t centralized,
                                mappo_stream_t stream);
+
+/* GPU-vectorised MPE simple_adversary, "physical deception" (csrc/mpe_adv_env.hip, device functions in csrc/mpe_adv_core.h): N
+ * environments of the fixed shape num_agents = 3 — agent 0 the ADVERSARY (observes the 2 landmarks relative to itself 4, the two
+ * others relative to itself 4 = 8 features; it is not told which landmark is the goal), agents 1 and 2 the GOOD agents (the goal
+ * landmark relative to themselves 2, then the same 8 = 10 features), 2 landmarks; every agent moves, Discrete(5); nobody speaks,
+ * nothing collides — one launch per step.  "Others" are in world-agent order, skipping the agent itself.  Replaces
+ * MultiAgentEnv.step / _set_action (environment.py:117-256: u = (a1 - a2, a3 - a4) * 5, accel is None), World.step (core.py:207-287:
+ * no environment forces, damping 0.25, dt 0.1, mass 1, no speed clamp), Scenario.reset_world / reward / observation
+ * (scenarios/simple_adversary.py:36-137) + the vec-env's reset-on-done (env_wrappers.py:146-152).  State is caller-owned device
+ * memory: agent_pos / agent_vel [N][3][2] and landmark_pos [N][2][2] in float64, goal [N] int32 (the landmark index of every
+ * agent's goal_a), tstep [N] int32, episode [N] int64 (reset counter = Philox counter).  Outputs: obs_adversary [N][8], obs_good1 /
+ * obs_good2 [N][10] fp32; rewards [N][3] fp32, ONE PER AGENT and never summed (world.collaborative is not set,
+ * environment.py:49-50,142): the adversary -|p_adv - p_goal|^2 (no square root), each good agent the same
+ * -min over the good agents of |p - p_goal| + |p_adv - p_goal| (square roots); dones [N][3] bool bytes.  action_mode 0: the
+ * reference's one-hots / probabilities, actions [N][3][5]; 1: indices as fp32, actions [N][3], clamped to 0..4 (1/2/3/4 =
+ * +x/-x/+y/-y).  Physics in float64 with contraction off and a correctly rounded sqrt: obs and rewards EQUAL the fp32 cast of the
+ * reference's float64 values.  An environment whose episode ends (tstep >= episode_length) is reset inside the same launch and
+ * returns the reset observation.  Reset draws: Philox stream (seed, episode), 64-bit uniform number 16 n + k of environment n —
+ * k = 2 a, 2 a + 1: position of agent a in U(-1,1); k = 6 + 2 l, 7 + 2 l: position of landmark l in U(-1,1); k = 10: goal =
+ * min(1, floor(2 u)), u in [0,1); k = 11..15 unused; velocities start at zero.  Both validate on the host and name the fault:
+ * num_agents == 3 (the only shape built), N >= 1, non-null pointers, action_mode 0 or 1, episode_length >= 1. */
+int mappo_mpe_adversary_reset(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *goal, int32_t *tstep,
+                              int64_t *episode, float *obs_adversary, float *obs_good1, float *obs_good2, int32_t N,
+                              int32_t num_agents, uint64_t seed, mappo_stream_t stream);
+int mappo_mpe_adversary_step(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *goal, int32_t *tstep,
+                             int64_t *episode, const float *actions, int32_t action_mode, float *obs_adversary, float *obs_good1,
+                             float *obs_good2, float *rewards, uint8_t *dones, int32_t N, int32_t num_agents,
+                             int32_t episode_length, uint64_t seed, mappo_stream_t stream);
+/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner
+ * (csrc/rollout_adversary.h): what T x (one mappo_rollout_step per agent + mappo_mpe_adversary_step with action_mode 1 + the
+ * agents' inserts) + one bootstrap mappo_rollout_step per agent do, bit for bit.  agents: the three mappo_comm_agent above
+ * (adversary, good agent 1, good agent 2).  Per step t < T: agent m's actor on its observation rows of step t (step 0: obs_buf
+ * slot 0), row n sampled with (agent's seed, counter + t (+ the agent's *counter_dev), Philox index n) -> actions / logp slot t;
+ * the environments step in float64 on the sampled indices (reset-on-done after env_episode_length steps); each agent's
+ * observation -> its obs_buf slot t + 1, its share row (centralized: the three observations side by side, 8 | 10 | 10 = 28; else
+ * its own observation) -> share_buf slot t + 1, its OWN reward -> rew_buf slot t, 1 - done -> mask_buf slot t + 1.  Each critic on
+ * its share rows of step t <= T -> values, step T -> next_values.  The six state arrays are stored back at the end, so the
+ * environment continues in either path.  Host checks, each named in the error: non-null descriptors; not recurrent; layer_N <= 1;
+ * actors in 8 / 10 / 10 and out 5; critics out 1 and in 28 (centralized) or the agent's own in_dim; the same layer_N and
+ * activation in all six networks; T, N, env_episode_length >= 1; non-null pointers. */
+int mappo_rollout_episode_adversary(const mappo_comm_agent *agents /*host, [3]*/, double *agent_pos, double *agent_vel,
+                                    double *landmark_pos, int32_t *goal, int32_t *tstep, int64_t *episode, int32_t T, int32_t N,
+                                    int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
+                                    int32_t centralized, mappo_stream_t stream);
 
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only

@@ -33,7 +33,7 @@ class SmacSlot(C.Structure):
 
 
 class CommAgent(C.Structure):
-    """mappo_comm_agent: one agent of mappo_rollout_episode_comm — networks, sampling seed, buffer arrays (include/mappo_hip.h)."""
+    """mappo_comm_agent: one agent of mappo_rollout_episode_comm / mappo_rollout_episode_adversary — networks, sampling seed, buffer arrays (include/mappo_hip.h)."""
     _fields_ = ([("actor_params", C.c_void_p), ("critic_params", C.c_void_p), ("actor_desc", NetDesc), ("critic_desc", NetDesc),
                  ("seed", C.c_uint64), ("counter_dev", C.c_void_p)] +
                 [(n, C.c_void_p) for n in ("obs_buf", "share_buf", "rew_buf", "mask_buf", "actions", "logp", "values", "next_values")])
@@ -130,6 +130,9 @@ SIGNATURES = {
     "mappo_mpe_comm_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _U64, _P]),
     "mappo_rollout_episode_comm": (C.c_int, [C.POINTER(CommAgent), C.POINTER(CommAgent), _I32, _I32, _I32, _U64, _P, _P, _P, _P, _P, _P, _P,
                                              _I32, _U64, _I32, _P]),
+    "mappo_mpe_adversary_reset": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _U64, _P]),
+    "mappo_mpe_adversary_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _P]),
+    "mappo_rollout_episode_adversary": (C.c_int, [C.POINTER(CommAgent), _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _I32, _U64, _I32, _P]),
     "mappo_profile_arm": (C.c_int, [_I32, _P, _P]),
     "mappo_selftest_mfma": (C.c_int, [_P, _P, _P, _P]),
 }

@@ -1,0 +1,208 @@
+// rollout_adversary.h — one rollout episode on the GPU-resident `simple_adversary` environment in ONE launch
+// (mappo_rollout_episode_adversary), for the SEPARATED runner: three agents (adversary 8 features, two good agents 10 each), each
+// with its own actor, critic, per-agent reward and SeparatedReplayBuffer.  It does what T x (three mappo_rollout_step +
+// mappo_mpe_adversary_step + the three agents' inserts) + the three bootstrap launches do, ~7 T + 3 dependent launches.
+//
+// The role skeleton of rollout_comm.h (read its header first): a tile is 16 whole environments, one workgroup of FOUR waves per
+// tile, one per SIMD, one row per environment and agent.  Six networks do not fit that kernel's plan of one network per wave in
+// registers: at layer_N 1 a network is ~290 VGPRs (mlp_ep16l.h), so six waves would put two on a SIMD, halve every wave's register
+// budget to 256 and spill; and six networks in the padded LDS image of mlp_ep16l.h are 6 x 45.7 KB = 274 KB against 160 KB per
+// CU.  So the agents are split by wave and the two networks of an agent by where their weights live:
+//   wave m = 0, 1, 2   agent m.  Its ACTOR has its weights in registers (Trunk16R / Head16R) — it is the step's critical path
+//           (actor -> environment -> actor): tile16r_step MODE 1 on the agent's slice of the observation tile, Philox (seed_m,
+//           counter + t (+ *counter_dev_m), row = environment), the sampled action also to the action tile.  Its CRITIC reads its
+//           weights from an LDS image (Trunk16L / Head16L of mlp_ep16l.h: the same 16-byte operands in the same order, so the same
+//           bits) and runs between the step's two barriers, beside the environment step; step T writes next_values.
+//   wave 3             the environments, lanes 0 .. 15: mpe_adv_step_env (mpe_adv_core.h) with mode 1 between the two barriers, the
+//           state in the lane for the whole episode; each agent's OWN reward -> its rew_buf[t], 1 - done -> its mask_buf[t + 1].
+//           Behind B_t the whole wave copies observation tile t + 1 into the three agents' obs[t + 1] / share_obs[t + 1] (what
+//           the stepwise insert writes), beside the actors of step t + 1.
+// and the same two workgroup barriers per step in every role (A_t: the actions of step t are in LDS and every read of observation
+// tile t is in registers; B_t: observation tile t + 1 is in LDS), behind one barrier that closes the staging of the critic images,
+// in which all four waves take part.  No role returns early: a wave whose rows or lanes do not exist (last partial tile) still
+// walks all T steps and their barriers.  An environment's three agents see the same environment step because the step sits behind
+// A_t, which all three actors of the tile have passed.
+//
+// LDS (floats): three critic images, EplMap<LN>::total each (11424 at layer_N 1, 6880 at 0) | the observation tile [16][28] — a row
+// is the adversary's 8 features, then the good agents' 10 and 10: the centralized share row as it stands, each network reads its
+// slice | one [16][TP] logits tile per actor wave | the action tile, one column of 16 per agent.  At layer_N 1 that is
+// 3 x 11424 + 448 + 3 x 528 + 48 = 36352 floats = 142 KB: one workgroup per CU, which the grid (N / 16 workgroups) does not exceed
+// before N = 4096 on 256 CUs.
+// Every value goes through the stepwise kernels' own code (tile16r_step, mpe_adv_step_env), so the three buffers and the
+// environment state end up bit-identical to the stepwise path's.
+#pragma once
+#include "mpe_adv_core.h"
+#include "rollout_comm.h"
+
+struct AdvEpisodeArgs {
+  CommNet a[MPE_ADV_M], c[MPE_ADV_M];            // per agent (0: adversary, 1 and 2: good agents)
+  MpeAdvArgs env;                                // state arrays, N, T = the ENV's episode length, mode 1, seed
+  float *obs_buf[MPE_ADV_M], *share_buf[MPE_ADV_M];        // [T + 1][N][D_m], [T + 1][N][S_m]
+  float *rew_buf[MPE_ADV_M], *mask_buf[MPE_ADV_M];         // [T][N], [T + 1][N]
+  float *next_values[MPE_ADV_M];                 // [N]: the critic at step T
+  uint64_t counter;
+  int T, centralized, deterministic;             // rollout steps
+};
+
+#define ADV_EP_G 16                                                 // environments per tile (workgroup)
+#define ADV_EP_WAVES 4
+#define ADV_X_TILE (16 * MPE_ADV_SHARE)
+template <int LN>
+constexpr int adv_ep_lds_floats() { return MPE_ADV_M * EplMap<LN>::total + ADV_X_TILE + MPE_ADV_M * 16 * TP + MPE_ADV_M * 16; }
+
+template <bool RELU, int LN>
+__global__ __launch_bounds__(ADV_EP_WAVES * WAVE, 1) void rollout_episode_adversary_kernel(AdvEpisodeArgs e) {
+  extern __shared__ __align__(16) float lds[];
+  constexpr int IMG = EplMap<LN>::total, W = MPE_ADV_SHARE;
+  float *X = lds + MPE_ADV_M * IMG, *tZ = X + ADV_X_TILE, *act = tZ + MPE_ADV_M * 16 * TP;
+  const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), j = lane & 15, q = lane >> 4;
+  const int T = e.T;
+  const int64_t B = e.env.N;                                        // rows of every buffer: one per environment
+  const int n0 = (int)blockIdx.x * ADV_EP_G;                        // first environment / buffer row of this tile
+  const int64_t i = (int64_t)n0 + j;
+  const bool ok = i < B;
+  const int jr = ok ? j : 0;
+  if (wave < MPE_ADV_M) {
+    // ---- agent m: actor (registers) and critic (LDS image); step 0 reads buffer slot 0, as the stepwise path does ----
+    const int m = wave;
+    const int D = mpe_adv_obs_dim(m), xo = mpe_adv_obs_off(m);
+    FwdArgs fa, fc;
+    comm_fwd_args(fa, e.a[m], B, e.deterministic);
+    comm_fwd_args(fc, e.c[m], B, 0);
+    const int S = fc.desc.in_dim, so_x = e.centralized ? 0 : xo;    // 28 (centralized) or D
+    f32x4 xa[4], xc[4];
+    spread_load_x(xa, e.obs_buf[m] + (ok ? i : 0) * D, D, q);
+    spread_load_x(xc, e.share_buf[m] + (ok ? i : 0) * S, S, q);
+    Trunk16R<LN> tw;
+    trunk16r_load<LN>(tw, fa.params, fa.off, fa.desc, j, q);
+    Head16R<1> hd;
+    head16r_load<1>(hd, fa.params, fa.off, fa.desc.out_dim, j, q);
+    const uint64_t ctr0 = e.counter + (e.a[m].counter_dev ? *e.a[m].counter_dev : 0ull);      // read once: the word is fixed for the launch
+#pragma unroll
+    for (int k = 0; k < MPE_ADV_M; ++k) epl_stage<LN, 1>(lds + k * IMG, e.c[k].params, e.c[k].off, e.c[k].desc);
+    __syncthreads();                                                // the critic images are staged
+    const float *img = lds + m * IMG;
+    const Trunk16L<LN> cw = {img + j * EPL_WS + 4 * q, img + 4 * q};
+    const Head16L<LN, 0> ch = {cw.m, cw.v};
+    for (int t = 0; t < T; ++t) {
+      const int64_t so = (int64_t)t * B;
+      tile16r_step<RELU, LN, 1, false, true>(fa, tw, hd, xa, nullptr, fa.actions + so, fa.logp + so, ctr0 + (uint64_t)t, nullptr,
+                                             tZ + m * 16 * TP, i, ok, j, q, act + m * 16);
+      __syncthreads();                                              // A_t
+      asm volatile("" ::: "memory");        // the image is loop-invariant: keep its reads inside the step (hoisted, they are a second register network)
+      tile16r_step<RELU, LN, 0>(fc, cw, ch, xc, fc.out + so, nullptr, nullptr, 0ull, nullptr, tZ + m * 16 * TP, i, ok, j, q);
+      __syncthreads();                                              // B_t
+      spread_load_x(xa, X + jr * W + xo, D, q);
+      spread_load_x(xc, X + jr * W + so_x, S, q);
+    }
+    asm volatile("" ::: "memory");
+    tile16r_step<RELU, LN, 0>(fc, cw, ch, xc, e.next_values[m], nullptr, nullptr, 0ull, nullptr, tZ + m * 16 * TP, i, ok, j, q);
+  } else {
+    // ---- the environments, one lane each, the state stays in the lane for the whole episode; the buffer's observation rows ----
+    const int n = n0 + lane;
+    const bool env_lane = lane < ADV_EP_G && n < e.env.N;
+    const int Rv = (int)(B - n0 < 16 ? B - n0 : 16);                // rows of the tile that exist (the last tile may be partial)
+    MpeAdvState s = {};
+    if (env_lane) mpe_adv_load(e.env, n, s);
+#pragma unroll
+    for (int k = 0; k < MPE_ADV_M; ++k) epl_stage<LN, 1>(lds + k * IMG, e.c[k].params, e.c[k].off, e.c[k].desc);
+    __syncthreads();                                                // the critic images are staged
+    for (int t = 0; t < T; ++t) {
+      const int64_t so = (int64_t)t * B;
+      __syncthreads();                                              // A_t
+      if (env_lane) {       // obs -> the tile's row, each agent's own reward -> slot t, masks -> slot t + 1 of its buffer
+        float reward[MPE_ADV_M];
+        float *row = X + lane * W;
+        const bool done = mpe_adv_step_env(e.env, n, act + lane, 16, s, row, row + mpe_adv_obs_off(1), row + mpe_adv_obs_off(2), reward);
+#pragma unroll
+        for (int k = 0; k < MPE_ADV_M; ++k) {
+          e.rew_buf[k][so + n] = reward[k];
+          e.mask_buf[k][so + B + n] = done ? 0.f : 1.f;
+        }
+      }
+      __syncthreads();                                              // B_t
+      // what the stepwise inserts write into slot t + 1 (centralized: the tile's row as it stands); the next write of the tile is this
+      // wave's own, behind A_{t + 1}
+#pragma unroll
+      for (int m = 0; m < MPE_ADV_M; ++m) {
+        const int D = mpe_adv_obs_dim(m), xo = mpe_adv_obs_off(m);
+        float *od = e.obs_buf[m] + (so + B + n0) * D;
+        for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; od[k] = X[r * W + xo + (k - r * D)]; }
+        if (e.centralized) {
+          float *sd = e.share_buf[m] + (so + B + n0) * W;
+          for (int k = lane; k < Rv * W; k += WAVE) sd[k] = X[k];
+        } else {
+          float *sd = e.share_buf[m] + (so + B + n0) * D;
+          for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; sd[k] = X[r * W + xo + (k - r * D)]; }
+        }
+      }
+    }
+    if (env_lane) mpe_adv_store(e.env, n, s, true);                 // the environment continues from here in either path
+  }
+}
+
+template <bool R, int L>
+static int adv_episode_launch(dim3 grid, hipStream_t st, const AdvEpisodeArgs &a) {
+  const size_t lds_bytes = sizeof(float) * adv_ep_lds_floats<L>();
+  static const hipError_t e_ = hipFuncSetAttribute((const void *)rollout_episode_adversary_kernel<R, L>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)(sizeof(float) * adv_ep_lds_floats<L>()));
+  if (e_ != hipSuccess) { mappo_set_error("rollout_episode_adversary: hipFuncSetAttribute: %s", hipGetErrorString(e_)); (void)hipGetLastError(); return MAPPO_ELAUNCH; }
+  hipLaunchKernelGGL((rollout_episode_adversary_kernel<R, L>), grid, dim3(ADV_EP_WAVES * WAVE), lds_bytes, st, a);
+  return MAPPO_OK;
+}
+
+extern "C" int mappo_rollout_episode_adversary(const mappo_comm_agent *agents, double *agent_pos, double *agent_vel, double *landmark_pos,
+                                               int32_t *goal, int32_t *tstep, int64_t *episode, int32_t T, int32_t N,
+                                               int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
+                                               int32_t centralized, mappo_stream_t stream) {
+  const char *who = "rollout_episode_adversary";
+  MAPPO_REQUIRE(agents, "%s: null agent descriptors (needs num_agents = 3 of them: adversary, good agent 1, good agent 2)", who);
+  const char *name[MPE_ADV_M] = {"adversary", "good agent 1", "good agent 2"};
+  for (int m = 0; m < MPE_ADV_M; ++m) {
+    const mappo_net_desc &da = agents[m].actor_desc, &dc = agents[m].critic_desc;
+    const int D = mpe_adv_obs_dim(m);
+    MAPPO_REQUIRE(!da.recurrent && !dc.recurrent, "%s: %s: recurrent networks take the stepwise path (this launch is feed-forward only)", who,
+                  name[m]);
+    MAPPO_REQUIRE(da.layer_N >= 0 && da.layer_N <= 1, "%s: %s: layer_N %d: this launch takes layer_N <= 1", who, name[m], da.layer_N);
+    if (int rc = check_desc(&da, who)) return rc;
+    if (int rc = check_desc(&dc, who)) return rc;
+    MAPPO_REQUIRE(da.in_dim == D && da.out_dim == MPE_ADV_U, "%s: %s actor in_dim %d / out_dim %d: simple_adversary has in_dim %d and %d "
+                  "actions there", who, name[m], da.in_dim, da.out_dim, D, MPE_ADV_U);
+    MAPPO_REQUIRE(dc.out_dim == 1, "%s: %s critic out_dim must be 1", who, name[m]);
+    if (centralized)
+      MAPPO_REQUIRE(dc.in_dim == MPE_ADV_SHARE, "%s: %s: centralized critic needs in_dim 8 + 10 + 10 = %d (got %d)", who, name[m],
+                    MPE_ADV_SHARE, dc.in_dim);
+    else
+      MAPPO_REQUIRE(dc.in_dim == D, "%s: %s critic in_dim %d != actor in_dim %d", who, name[m], dc.in_dim, D);
+    MAPPO_REQUIRE(da.layer_N == agents[0].actor_desc.layer_N && dc.layer_N == da.layer_N && da.use_relu == agents[0].actor_desc.use_relu &&
+                  dc.use_relu == da.use_relu, "%s: all six networks must share layer_N and the activation", who);
+  }
+  MAPPO_REQUIRE(T >= 1 && N >= 1 && env_episode_length >= 1, "%s: bad shape T=%d N=%d env episode length %d (each needs >= 1)", who, T, N,
+                env_episode_length);
+  MAPPO_REQUIRE(agent_pos && agent_vel && landmark_pos && goal && tstep && episode, "%s: bad arguments (null state pointer)", who);
+  for (int m = 0; m < MPE_ADV_M; ++m)
+    MAPPO_REQUIRE(agents[m].actor_params && agents[m].critic_params && agents[m].obs_buf && agents[m].share_buf && agents[m].rew_buf &&
+                  agents[m].mask_buf && agents[m].actions && agents[m].logp && agents[m].values && agents[m].next_values,
+                  "%s: bad arguments (null pointer, %s)", who, name[m]);
+  MAPPO_CLEAR_STICKY();
+  AdvEpisodeArgs e = {};
+  for (int m = 0; m < MPE_ADV_M; ++m) {
+    const mappo_comm_agent &ag = agents[m];
+    e.a[m].params = ag.actor_params; e.a[m].actions = ag.actions; e.a[m].logp = ag.logp; e.a[m].desc = ag.actor_desc;
+    e.a[m].off = net_offsets(e.a[m].desc); e.a[m].seed = ag.seed; e.a[m].counter_dev = ag.counter_dev;
+    e.c[m].params = ag.critic_params; e.c[m].out = ag.values; e.c[m].desc = ag.critic_desc; e.c[m].off = net_offsets(e.c[m].desc);
+    e.obs_buf[m] = ag.obs_buf; e.share_buf[m] = ag.share_buf; e.rew_buf[m] = ag.rew_buf; e.mask_buf[m] = ag.mask_buf;
+    e.next_values[m] = ag.next_values;
+  }
+  e.env.apos = agent_pos; e.env.avel = agent_vel; e.env.lpos = landmark_pos; e.env.goal = goal; e.env.tstep = tstep; e.env.episode = episode;
+  e.env.N = N; e.env.T = env_episode_length; e.env.mode = 1; e.env.seed = env_seed;
+  e.counter = counter; e.T = T; e.centralized = centralized; e.deterministic = deterministic;
+  const dim3 grid((unsigned)((N + ADV_EP_G - 1) / ADV_EP_G));
+  const bool relu = agents[0].actor_desc.use_relu != 0;
+  int rc;
+  if (agents[0].actor_desc.layer_N == 0) rc = relu ? adv_episode_launch<true, 0>(grid, as_stream(stream), e) : adv_episode_launch<false, 0>(grid, as_stream(stream), e);
+  else rc = relu ? adv_episode_launch<true, 1>(grid, as_stream(stream), e) : adv_episode_launch<false, 1>(grid, as_stream(stream), e);
+  if (rc) return rc;
+  MAPPO_CHECK_LAUNCH("rollout_episode_adversary");
+  return MAPPO_OK;
+}

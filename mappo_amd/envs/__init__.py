@@ -1,1 +1,2 @@
 from .mpe_speaker_listener import SimpleSpeakerListenerVecEnv  # noqa: F401
+from .mpe_adversary import SimpleAdversaryVecEnv  # noqa: F401

@@ -390,7 +390,7 @@ def rollout_episode_reference(actor_params, actor_desc, critic_params, critic_de
 
 def comm_agent(actor_params, actor_desc, critic_params, critic_desc, seed, counter_dev, obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values,
                next_values):
-    """One agent of rollout_episode_comm (mappo_comm_agent): its networks, its sampling seed and counter word (int64 [1] device tensor or None) and the contiguous arrays of its
+    """One agent of rollout_episode_comm / rollout_episode_adversary (mappo_comm_agent): its networks, its sampling seed and counter word (int64 [1] device tensor or None) and the contiguous arrays of its
     SeparatedReplayBuffer."""
     ag = _lib.CommAgent()
     ag.actor_params, ag.critic_params = _ptr(actor_params).value, _ptr(critic_params).value
@@ -416,6 +416,23 @@ def rollout_episode_comm(speaker, listener, T, N, env_episode_length, env_seed, 
                                                 _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(bool(deterministic)),
                                                 int(counter) & (2 ** 64 - 1), int(bool(centralized)), _stream())
     _lib.check(rc, "mappo_rollout_episode_comm")
+
+
+def rollout_episode_adversary(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
+                              deterministic, counter, centralized):
+    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_adversary env in one launch, env steps included
+    (mappo_rollout_episode_adversary).  agents: the three comm_agent(...) of agents 0 (adversary), 1, 2 (good); the six env state
+    tensors (SimpleAdversaryVecEnv) are read, stepped T times on the sampled indices and stored back."""
+    if len(agents) != 3:
+        raise ValueError(f"rollout_episode_adversary: simple_adversary is built for num_agents = 3 (got {len(agents)} agents)")
+    f64 = torch.float64
+    arr = (_lib.CommAgent * 3)(*agents)
+    rc = _lib.load().mappo_rollout_episode_adversary(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
+                                                     _ptr(goal, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T),
+                                                     int(N), int(env_episode_length), int(env_seed) & (2 ** 64 - 1),
+                                                     int(bool(deterministic)), int(counter) & (2 ** 64 - 1), int(bool(centralized)),
+                                                     _stream())
+    _lib.check(rc, "mappo_rollout_episode_adversary")
 
 
 def mlp_backward_slabs(B):
@@ -743,6 +760,26 @@ def mpe_comm_step(listener_pos, listener_vel, landmark_pos, goal, symbol, tstep,
                                          _ptr(obs_listener), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length),
                                          int(seed) & (2 ** 64 - 1), _stream())
     _lib.check(rc, "mappo_mpe_comm_step")
+
+
+# ---- GPU-vectorised MPE simple_adversary (csrc/mpe_adv_env.hip): adversary + two good agents, Discrete(5) each, per-agent rewards ------
+def mpe_adversary_reset(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, obs_adversary, obs_good1, obs_good2, N, seed, num_agents=3):
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_adversary_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                               _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs_adversary), _ptr(obs_good1),
+                                               _ptr(obs_good2), int(N), int(num_agents), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_adversary_reset")
+
+
+def mpe_adversary_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, actions, action_mode, obs_adversary, obs_good1, obs_good2,
+                       rewards, dones, N, episode_length, seed, num_agents=3):
+    """action_mode 0: one-hots [N, 3, 5] | 1: fp32 indices [N, 3].  rewards [N, 3]: one per agent."""
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_adversary_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                              _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(actions), int(action_mode),
+                                              _ptr(obs_adversary), _ptr(obs_good1), _ptr(obs_good2), _ptr(rewards), _ptr(dones, torch.uint8),
+                                              int(N), int(num_agents), int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_adversary_step")
 
 
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):

@@ -2,7 +2,8 @@
 and SeparatedReplayBuffer PER AGENT (lists indexed by agent id), all on the HIP kernels of the shared path.  Every agent's
 networks live in their own flat parameter buffer; `compute` / `train` run the agents one after the other (the same
 launches as the shared runner with M = 1).  The ROLLOUT of agents with feed-forward policies on the GPU-resident
-simple_speaker_listener env is batched into one launch (separated/mpe_runner.py, mappo_rollout_episode_comm); batching the agents'
+simple_speaker_listener and simple_adversary envs is batched into one launch (separated/mpe_runner.py,
+mappo_rollout_episode_comm / mappo_rollout_episode_adversary); batching the agents'
 PPO updates is the next step."""
 import os
 

@@ -10,7 +10,9 @@ observations are then a list of per-agent tensors (mappo_amd.envs.mpe_speaker_li
 array [N, M] of per-agent arrays; one-hot widths come from each agent's own action space.  On such an env feed-forward policies
 collect through mappo_rollout_step (one launch per agent for actor + critic), and on the GPU-resident speaker-listener env the
 whole episode — both agents' networks, the env steps and the inserts — is ONE launch (mappo_rollout_episode_comm) with the same
-buffer contents and env state, bit for bit; MAPPO_COMM_EPISODE=0 keeps the stepwise path (A/B runs, tests)."""
+buffer contents and env state, bit for bit; MAPPO_COMM_EPISODE=0 keeps the stepwise path (A/B runs, tests).  The GPU-resident
+simple_adversary env (three agents, observations of 8 / 10 / 10 features, per-agent rewards) runs the same two ways:
+mappo_rollout_episode_adversary, MAPPO_ADV_EPISODE=0 for the stepwise path."""
 import os
 import time
 
@@ -69,6 +71,9 @@ class MPERunner(Runner):
                 p.actor._counter_dev.add_(self.episode_length)
         if self._comm_episode_ready():
             self._collect_episode_comm(deterministic)
+            return infos
+        if self._adversary_episode_ready():
+            self._collect_episode_adversary(deterministic)
             return infos
         for step in range(self.episode_length):
             values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env = self.collect(step, deterministic)
@@ -144,9 +149,14 @@ class MPERunner(Runner):
         env = self.envs
         if os.environ.get("MAPPO_COMM_EPISODE", "1") == "0" or not hasattr(env, "episode_state_comm") or self.num_agents != 2:
             return False
+        return self._episode_shapes_ready(env, env.listener_pos.device)
+
+    def _episode_shapes_ready(self, env, dev):
+        """What the one-launch episodes of the ragged envs share: feed-forward narrow policies, layer_N <= 1, one layer_N and
+        activation in all networks, the env's own widths, buffers in the device layout the launch writes.  dev: where the env's
+        tensors landed."""
         if not self._fused_ff():
             return False
-        dev = env.listener_pos.device                           # where its tensors landed
         d0 = self.policy[0].actor.desc
         S = sum(env.obs_dims)
         for agent_id, p in enumerate(self.policy):
@@ -175,6 +185,33 @@ class MPERunner(Runner):
         ops.rollout_episode_comm(ags[0], ags[1], self.episode_length, N, st["T"], st["seed"], st["listener_pos"], st["listener_vel"],
                                  st["landmark_pos"], st["goal"], st["symbol"], st["tstep"], st["episode"], deterministic, 0,
                                  self.use_centralized_V)
+        for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
+            b.step = 0
+            tr.prep_rollout()
+            b.compute_returns(self._next_values[agent_id], tr.value_normalizer)
+
+    # ---- the same on simple_adversary (mappo_rollout_episode_adversary) ----
+    def _adversary_episode_ready(self):
+        """The env is the GPU-resident simple_adversary and the three policies are what the kernel is built for; anything else
+        takes the stepwise path."""
+        env = self.envs
+        if os.environ.get("MAPPO_ADV_EPISODE", "1") == "0" or not hasattr(env, "episode_state_adversary") or self.num_agents != 3:
+            return False
+        return self._episode_shapes_ready(env, env.agent_pos.device)
+
+    @torch.no_grad()
+    def _collect_episode_adversary(self, deterministic=False):
+        """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent."""
+        st = self.envs.episode_state_adversary()
+        N = self.n_rollout_threads
+        if self._next_values is None:
+            self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
+        from mappo_amd import ops
+        ags = [ops.comm_agent(p.actor.flat, p.actor.desc, p.critic.flat, p.critic.desc, p.actor._seed, p.actor._counter_dev, b.obs, b.share_obs,
+                              b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds, self._next_values[agent_id])
+               for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer))]
+        ops.rollout_episode_adversary(ags, self.episode_length, N, st["T"], st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"],
+                                      st["goal"], st["tstep"], st["episode"], deterministic, 0, self.use_centralized_V)
         for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
             b.step = 0
             tr.prep_rollout()
