@@ -326,6 +326,24 @@ int mappo_update_stats(const double *actor_partials, int32_t n_actor /*workgroup
                        double *acc /*[>=4] running sums of stats[0..3] over the updates of one train(), or NULL*/,
                        mappo_stream_t stream);
 
+/* ---- once-per-train() glue of a whole-buffer update (every epoch's minibatch is the buffer), fused ---------------------
+ * mappo_train_prologue = mappo_adv_moments + mappo_minibatch_moments (rows NULL, B = n) + mappo_valuenorm_update_n + a fill, in ONE
+ * launch with bit-identical results: adv [n] (raw; mappo_adv_normalize follows as its own launch), adv_moments [3],
+ * mb_moments [4], and, when vn_state is not NULL, the n_epochs ValueNorm states (states_out, vn_state; the advantages use the
+ * state from before the call).  zero[0..n_zero) is set to 0.0 (n_zero may be 0).  The workgroup that finishes last does the
+ * one-workgroup work; `ticket` is ONE int32 word that must be 0 before the first call and is 0 again after every call (so the
+ * call can be captured into a hipGraph and replayed); workspace (mappo_train_prologue_workspace_bytes) and ticket must not be
+ * shared by calls that may run concurrently. */
+int64_t mappo_train_prologue_workspace_bytes(int64_t n);
+int mappo_train_prologue(const float *returns /*[n]*/, const float *value_preds /*[n]*/, const float *active_masks /*[n]*/,
+                         float *vn_state /*[3] in/out or NULL*/, float *adv /*[n] out (raw)*/, double *adv_moments /*[3] out*/,
+                         double *mb_moments /*[4] out*/, double beta, int32_t n_epochs, float *states_out /*[n_epochs][3] or NULL*/,
+                         double *zero, int64_t n_zero, void *workspace, int32_t *ticket, int64_t n, mappo_stream_t stream);
+/* mappo_train_epilogue = mappo_update_stats + mappo_copy_batch (same arguments, same results) in one launch. */
+int mappo_train_epilogue(const double *actor_partials, int32_t n_actor, const double *critic_partials, int32_t n_critic,
+                         const double *mb_moments, const mappo_ppo_cfg *cfg /*host*/, double *stats /*[6]*/, double *acc,
+                         int32_t count, float *const *dst, const float *const *src, const int64_t *n_floats, mappo_stream_t stream);
+
 /* ---- K9: recurrent layer (onpolicy/algorithms/utils/rnn.py:7-80: nn.GRU(64,64) with per-step h*mask + LayerNorm) ----
  * A recurrent network = trunk (mappo_mlp_features) -> GRU -> rnn.norm -> head.  Outside the training pass (below: the
  * mappo_gru16_* entry points) features are feature-major: featT is [64][B], B = L*Nc, column t*Nc + c (time-major over Nc

@@ -92,6 +92,10 @@ SIGNATURES = {
     "mappo_actor_critic_update_md": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, C.POINTER(NetDesc), _P, _P, _I64, _P, C.POINTER(_I32), _I32,
                                                _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(PpoCfg), _P, _I64, _I64, _I64, _P, _P, _P]),
     "mappo_update_stats": (C.c_int, [_P, _I32, _P, _I32, _P, C.POINTER(PpoCfg), _P, _P, _P]),
+    "mappo_train_prologue_workspace_bytes": (_I64, [_I64]),
+    "mappo_train_prologue": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _D, _I32, _P, _P, _I64, _P, _P, _I64, _P]),
+    "mappo_train_epilogue": (C.c_int, [_P, _I32, _P, _I32, _P, C.POINTER(PpoCfg), _P, _P, _I32, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.POINTER(_I64), _P]),
     "mappo_mlp_features": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _I64, _P, _P]),
     "mappo_gru_forward": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _U64, _U64,
                                     _P, _P, _P, _P]),

@@ -53,6 +53,7 @@ class R_MAPPO():
         self._fused = not bool(getattr(args, "unfused_update", False))
         self._use_graph = bool(getattr(args, "use_hip_graph", True))
         self._concurrent_update = bool(getattr(args, "concurrent_update", False))
+        self._fuse_glue = bool(getattr(args, "fuse_train_glue", True))
         self._graphs = {}
         self._dp_graphs = {}                       # data-parallel runs: hipGraphs of the collective-free segments
         self._graph_buffers = {}                   # id(buffer) -> buffer: referenced for as long as its graphs are cached
@@ -324,9 +325,6 @@ class R_MAPPO():
     def _train_body(self, buffer, update_actor, after_update):
         T = buffer.episode_length
         S = T * buffer.n_rollout_threads * buffer.num_agents
-        adv = self.compute_advantages(buffer)
-        src, _ = self._buffer_sources(buffer, adv)
-        self._zbuf.zero_()
         whole = self.num_mini_batch == 1 and not self._exact_order
         dp_graph = self._dist is not None and self._use_graph and whole and self._fused and self._dist.world_is_gpu
         key = (self._buffer_key(buffer), bool(update_actor))
@@ -336,6 +334,16 @@ class R_MAPPO():
             # every update sees the same minibatch (the whole buffer): ValueNorm's ppo_epoch updates are one launch, the
             # loss sums accumulate in the kernels' partials and the statistics kernel runs once after the last epoch
             self._epochs = dict(n=self.ppo_epoch, e=0, states=self._buf("vn_states", (self.ppo_epoch, 3)))
+        # single process, whole-buffer epochs: nothing sits between the moments and their use, so advantages, the fill of
+        # _zbuf, the minibatch moments and the ValueNorm updates are ONE launch (+ the normalisation), and the statistics
+        # share a launch with after_update's copies
+        glue = self._fuse_glue and self._epochs is not None and self._dist is None
+        if glue:
+            adv = self._train_prologue(buffer)
+        else:
+            adv = self.compute_advantages(buffer)
+            self._zbuf.zero_()
+        src, _ = self._buffer_sources(buffer, adv)
         if dp_graph:
             # data parallel: the moments (one 4-double all-reduce) come first, so that EVERY epoch is the same collective-free
             # kernel segment (captured per epoch: the ValueNorm state an epoch reads sits at its own address)
@@ -375,14 +383,20 @@ class R_MAPPO():
                         st.replay()
                     self._update(src, rows, B, update_actor, moments_ready=True, part="optim")
                 else:
-                    self._update(src, rows, B, update_actor, moments_ready=whole and epoch > 0)
+                    self._update(src, rows, B, update_actor, moments_ready=glue or (whole and epoch > 0))
         if self._epochs is not None:
             # (rows of loss partials the update kernels wrote; not taken from a side effect of _update_kernels: under data
             # parallelism the epochs may have been graph replays, during which no Python runs)
             n_rows = ops.dual_update_slabs(self.policy.actor.desc, self.policy.critic.desc, S) if (update_actor and self._dual_update and self.policy.can_dual_update()) \
                 else ops.mlp_backward_slabs(S)
-            ops.update_stats(self._pa if update_actor else None, n_rows, self._pc, n_rows, self._mb_moments, self._cfg, self._stats,
-                             self._acc)
+            pairs = buffer.after_update_pairs() if (glue and after_update) else None
+            if pairs:
+                ops.train_epilogue(self._pa if update_actor else None, n_rows, self._pc, n_rows, self._mb_moments, self._cfg,
+                                   self._stats, self._acc, pairs)
+                after_update = False                           # done in that launch
+            else:
+                ops.update_stats(self._pa if update_actor else None, n_rows, self._pc, n_rows, self._mb_moments, self._cfg,
+                                 self._stats, self._acc)
             self._epochs = None
         if dp_graph and self._dp_graphs.get(key) is None:
             self._dp_graphs[key] = "warm"                      # first train() ran eagerly: workspaces exist now
@@ -403,11 +417,31 @@ class R_MAPPO():
         ops.adv_normalize(adv, self._adv_moments)
         return adv
 
+    def _train_prologue(self, buffer):
+        """compute_advantages + _zbuf.zero_() + _moments of the first epoch: mappo_train_prologue, then the normalisation."""
+        T = buffer.episode_length
+        S = T * buffer.n_rollout_threads * buffer.num_agents
+        adv = self._buf("adv", (S,))
+        if self._glue_ws is None:
+            self._glue_ws = ops.train_prologue_workspace(S, self.device)
+        vn = self.value_normalizer if self._use_valuenorm else None
+        ep = self._epochs
+        ops.train_prologue(buffer.returns[:T].view(S), buffer.value_preds[:T].view(S), buffer.active_masks[:T].view(S),
+                           vn.state if vn is not None else None, adv, self._adv_moments, self._mb_moments,
+                           vn.beta if vn is not None else 0.0, ep["n"], ep["states"] if vn is not None else None, self._zbuf, *self._glue_ws)
+        ops.adv_normalize(adv, self._adv_moments)
+        return adv
+
+    _glue_ws = None
+
     def _finish_train_info(self):
         num_updates = self.ppo_epoch * self.num_mini_batch
         if self._dist is not None:
             self._dist.all_reduce_sum_(self._acc[:4])          # local numerators / global denominators -> global stats
-        acc = (self._acc / max(num_updates, 1)).cpu().numpy()    # the only host sync of train()
+        # the only host sync of train().  The mean is taken on the host in float64 as acc * (1 / num_updates): the product
+        # with the reciprocal is what the device-side `tensor / int` it replaces computed (torch multiplies by the
+        # reciprocal of a host scalar), so the statistics keep their bits and one launch in front of the sync is gone
+        acc = self._acc.cpu().numpy() * (np.float64(1.0) / np.float64(max(num_updates, 1)))
         return dict(value_loss=float(acc[0]), policy_loss=float(acc[1]), dist_entropy=float(acc[2]),
                     actor_grad_norm=float(acc[4]), critic_grad_norm=float(acc[5]), ratio=float(acc[3]))
 

@@ -103,6 +103,11 @@ def get_config():
                         "steps run inside that launch too (mappo_rollout_episode_spread), and so they do with the GPU-resident simple_reference env "
                         "and its MultiDiscrete (5, 10) policy (SimpleReferenceVecEnv, mappo_rollout_episode_reference); pass the flag to run "
                         "the stepwise loop")
+    p.add_argument("--fuse_train_glue", **off,
+                   help="by default a single-process whole-buffer train() runs its once-per-call work in two launches "
+                        "(mappo_train_prologue: advantages, both moment reductions, the ValueNorm updates, the fill of the "
+                        "statistics buffer; mappo_train_epilogue: statistics + after_update); pass the flag to use the separate "
+                        "launches; same results")
     p.add_argument("--dual_update", **off,
                    help="by default the actor's and the critic's fused update run in ONE launch, half the CUs each "
                         "(mappo_actor_critic_update); pass the flag to launch them one after the other")

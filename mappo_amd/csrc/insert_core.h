@@ -134,3 +134,33 @@ __device__ __forceinline__ void insert_smac_body(const SmacInsert &p, int bid, i
   }
 }
 
+
+// after_update (see mappo_copy_batch): up to 16 independent device copies by `nb` cooperating 256-thread workgroups, this one `bid`
+#define COPY_MAX 16
+struct CopyBatch {
+  float *dst[COPY_MAX];
+  const float *src[COPY_MAX];
+  int64_t n[COPY_MAX];          // floats
+  int count;
+};
+static inline int copy_batch_blocks(int64_t total_floats) {
+  int64_t nb = (total_floats / 4 + 255) / 256;
+  if (nb < 1) nb = 1;
+  if (nb > 1024) nb = 1024;
+  return (int)nb;
+}
+__device__ __forceinline__ void copy_batch_body(const CopyBatch &c, int bid, int nb) {
+  for (int j = 0; j < c.count; ++j) {
+    const float *__restrict__ s = c.src[j];
+    float *__restrict__ d = c.dst[j];
+    const int64_t n = c.n[j];
+    if (((((uintptr_t)s) | ((uintptr_t)d)) & 15) == 0) {
+      const int64_t n4 = n >> 2;
+      for (int64_t i = (int64_t)bid * blockDim.x + threadIdx.x; i < n4; i += (int64_t)nb * blockDim.x)
+        reinterpret_cast<float4 *>(d)[i] = reinterpret_cast<const float4 *>(s)[i];
+      for (int64_t i = (n4 << 2) + (int64_t)bid * blockDim.x + threadIdx.x; i < n; i += (int64_t)nb * blockDim.x) d[i] = s[i];
+    } else {
+      for (int64_t i = (int64_t)bid * blockDim.x + threadIdx.x; i < n; i += (int64_t)nb * blockDim.x) d[i] = s[i];
+    }
+  }
+}

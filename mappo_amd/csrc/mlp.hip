@@ -7,6 +7,7 @@
 #include "mlp_upd.h"             // UPD_THREADS
 #include "mlp_upd2.h"            // DualArgs
 #include "mlp_upd16.h"           // Upd16Args, Dual16Args, L16
+#include "stats_core.h"          // update_stats_body
 #include <stdlib.h>
 
 #ifdef MLP_STAMPS                // diagnostic build (scripts/stamps*.py): the buffers the update kernels flush their stamps to
@@ -798,22 +799,7 @@ __global__ __launch_bounds__(256) void update_stats_kernel(const double *__restr
                                                           int use_value_active, double *__restrict__ stats,
                                                           double *__restrict__ acc) {
   __shared__ double smem[16 * 4];
-  double v[4] = {0.0, 0.0, 0.0, 0.0};    // sum w*min, sum w*H, sum ratio, sum w_v*l
-  for (int b = threadIdx.x; b < na; b += blockDim.x) { v[0] += pa[b * 4 + 0]; v[1] += pa[b * 4 + 1]; v[2] += pa[b * 4 + 2]; }
-  for (int b = threadIdx.x; b < nc; b += blockDim.x) v[3] += pc[b * 4 + 0];
-  block_sum<4>(v, smem);
-  if (threadIdx.x == 0) {
-    const double sa = mb_moments[2] > 0.0 ? mb_moments[2] : 1.0;
-    const double Bg = mb_moments[3] > 0.0 ? mb_moments[3] : 1.0;
-    const double den_pi = use_policy_active ? sa : Bg, den_v = use_value_active ? sa : Bg;
-    stats[0] = v[3] / den_v;
-    stats[1] = -v[0] / den_pi;
-    stats[2] = v[1] / den_pi;
-    stats[3] = v[2] / Bg;
-    stats[4] = mb_moments[2];
-    stats[5] = mb_moments[3];
-    if (acc) { acc[0] += stats[0]; acc[1] += stats[1]; acc[2] += stats[2]; acc[3] += stats[3]; }   // train_info sums (r_mappo.py:207-212)
-  }
+  update_stats_body(pa, pc, na, nc, mb_moments, use_policy_active, use_value_active, stats, acc, smem);
 }
 
 extern "C" int mappo_update_stats(const double *actor_partials, int32_t n_actor, const double *critic_partials,

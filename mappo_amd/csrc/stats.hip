@@ -2,17 +2,7 @@
 // valuenorm.py:37-54) and the minibatch denominators the fused loss needs (r_mappo.py:84,130-134).
 // All reductions: per-thread double accumulation -> wave shuffle -> per-block partial -> one-block final
 // pass, i.e. deterministic (no atomics) and far inside the 1e-5 budget for fp32 statistics.
-#include "common.h"
-
-#define STAT_BLOCK 256
-#define STAT_MAX_BLOCKS 1024
-
-static inline int stat_blocks(int64_t n) {
-  int64_t b = (n + STAT_BLOCK * 4 - 1) / (STAT_BLOCK * 4);
-  if (b < 1) b = 1;
-  if (b > STAT_MAX_BLOCKS) b = STAT_MAX_BLOCKS;
-  return (int)b;
-}
+#include "stats_core.h"
 
 // out[0..NV) = sum of the per-block partials; out[NV] = `extra` when extra >= 0 (the minibatch size B)
 template <int NV>
@@ -20,13 +10,7 @@ __global__ __launch_bounds__(STAT_BLOCK) void final_reduce_kernel(const double *
                                                                  double *__restrict__ out, double extra) {
   __shared__ double smem[16 * NV];
   double v[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += blockDim.x) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] += partials[(size_t)b * NV + i];
-  }
-  block_sum<NV>(v, smem);
+  final_reduce_sum<NV>(partials, nblk, v, smem);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) out[i] = v[i];
@@ -45,15 +29,8 @@ __global__ __launch_bounds__(STAT_BLOCK) void adv_moments_kernel(const float *__
   const VnStats vn = vn_stats(vn_state);
   double v[3] = {0.0, 0.0, 0.0};
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float a = returns[i] - (value_preds[i] * vn.sd + vn.mean);   // r_mappo.py:174-177
-    adv[i] = a;
-    if (active[i] != 0.f) {                                             // :178-181 (nanmean / nanstd)
-      v[0] += (double)a;
-      v[1] += (double)a * (double)a;
-      v[2] += 1.0;
-    }
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    adv_moments_term(returns[i], value_preds[i], active[i], vn, adv + i, v);
   block_sum<3>(v, smem);
   if (threadIdx.x == 0) {
     partials[blockIdx.x * 3 + 0] = v[0];
@@ -109,10 +86,7 @@ __global__ __launch_bounds__(STAT_BLOCK) void minibatch_moments_kernel(const flo
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < B; i += stride) {
     const int64_t row = rows ? (int64_t)rows[i] : i;
-    const float r = returns[row];
-    v[0] += (double)r;
-    v[1] += (double)r * (double)r;
-    v[2] += (double)active[row];
+    minibatch_moments_term(returns[row], active[row], v);
   }
   block_sum<3>(v, smem);
   if (threadIdx.x == 0) {
@@ -157,17 +131,7 @@ extern "C" int mappo_valuenorm_update(float *vn_state, const double *mb_moments,
 }
 
 __global__ void valuenorm_update_n_kernel(float *vn_state, const double *mb_moments, float w, float omw, int n, float *states_out) {
-  const double B = mb_moments[3] > 0.0 ? mb_moments[3] : 1.0;
-  const float bm = (float)(mb_moments[0] / B);
-  const float bsq = (float)(mb_moments[1] / B);
-  float s0 = vn_state[0], s1 = vn_state[1], s2 = vn_state[2];
-  for (int e = 0; e < n; ++e) {
-    s0 = __fadd_rn(__fmul_rn(s0, w), __fmul_rn(bm, omw));
-    s1 = __fadd_rn(__fmul_rn(s1, w), __fmul_rn(bsq, omw));
-    s2 = __fadd_rn(__fmul_rn(s2, w), omw);
-    states_out[3 * e + 0] = s0; states_out[3 * e + 1] = s1; states_out[3 * e + 2] = s2;
-  }
-  vn_state[0] = s0; vn_state[1] = s1; vn_state[2] = s2;
+  valuenorm_update_n_body(vn_state, mb_moments[0], mb_moments[1], mb_moments[3], w, omw, n, states_out);
 }
 
 extern "C" int mappo_valuenorm_update_n(float *vn_state, const double *mb_moments, double beta, int32_t n, float *states_out,

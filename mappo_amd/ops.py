@@ -543,6 +543,43 @@ def update_stats(actor_partials, n_actor, critic_partials, n_critic, mb_moments,
     _lib.check(rc, "mappo_update_stats")
 
 
+def _copy_lists(pairs):
+    n = len(pairs)
+    for d, s_ in pairs:
+        assert d.is_cuda and s_.is_cuda and d.dtype == torch.float32 and s_.dtype == torch.float32 and d.is_contiguous() \
+            and s_.is_contiguous() and d.numel() == s_.numel()
+    return (n, (C.c_void_p * n)(*[d.data_ptr() for d, _ in pairs]), (C.c_void_p * n)(*[s.data_ptr() for _, s in pairs]),
+            (C.c_int64 * n)(*[d.numel() for d, _ in pairs]))
+
+
+# ---- once-per-train() glue of a whole-buffer update ---------------------------------------------------
+def train_prologue_workspace(n, device):
+    """(workspace, ticket) of train_prologue: allocate once, the ticket zeroed; every call leaves it zero again."""
+    return _ws(_lib.load().mappo_train_prologue_workspace_bytes(int(n)), device), torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def train_prologue(returns, value_preds, active_masks, vn_state, adv, adv_moments, mb_moments, beta, n_epochs, states_out, zero,
+                   workspace, ticket):
+    """adv_moments + minibatch_moments(rows=None) + valuenorm_update_n (vn_state not None) + zero.zero_() in ONE launch, bit-identical
+    to them; adv_normalize follows as its own launch.  zero: contiguous float64 tensor or None."""
+    rc = _lib.load().mappo_train_prologue(_ptr(returns), _ptr(value_preds), _ptr(active_masks), _ptr(vn_state, allow_none=True), _ptr(adv),
+                                          _ptr(adv_moments, torch.float64), _ptr(mb_moments, torch.float64), float(beta), int(n_epochs),
+                                          _ptr(states_out, allow_none=True), _ptr(zero, torch.float64, allow_none=True),
+                                          zero.numel() if zero is not None else 0, _ptr(workspace, torch.uint8),
+                                          _ptr(ticket, torch.int32), adv.numel(), _stream())
+    _lib.check(rc, "mappo_train_prologue")
+
+
+def train_epilogue(actor_partials, n_actor, critic_partials, n_critic, mb_moments, cfg, stats, acc, pairs):
+    """update_stats(...) + copy_batch(pairs) in ONE launch, bit-identical to them."""
+    n, dst, src, cnt = _copy_lists(pairs)
+    rc = _lib.load().mappo_train_epilogue(_ptr(actor_partials, torch.float64, allow_none=True), int(n_actor),
+                                          _ptr(critic_partials, torch.float64), int(n_critic), _ptr(mb_moments, torch.float64),
+                                          C.byref(cfg), _ptr(stats, torch.float64), _ptr(acc, torch.float64, allow_none=True),
+                                          n, dst, src, cnt, _stream())
+    _lib.check(rc, "mappo_train_epilogue")
+
+
 # ---- K9: recurrent layer -------------------------------------------------------------------------
 def mlp_features(params, desc, x, rows, B, featT):
     rc = _lib.load().mappo_mlp_features(_ptr(params), C.byref(desc), _ptr(x), _ptr(rows, torch.int32, allow_none=True), int(B),

@@ -185,9 +185,14 @@ class SharedReplayBuffer(object):
 
     def after_update(self):
         """shared_buffer.py:114-131: slot T of every carried array becomes slot 0 — one launch (mappo_copy_batch)."""
+        ops.copy_batch(self.after_update_pairs())
+
+    def after_update_pairs(self):
+        """The (dst, src) copies after_update() performs, for a caller that runs them inside a launch of its own
+        (R_MAPPO.train: mappo_train_epilogue)."""
         arrs = [a for a in (self.share_obs, self.obs, self.rnn_states, self.rnn_states_critic, self.masks, self.bad_masks,
                             self.active_masks, self.available_actions) if a is not None]
-        ops.copy_batch([(a[0], a[-1]) for a in arrs])
+        return [(a[0], a[-1]) for a in arrs]
 
     def chooseafter_update(self):
         for arr in (self.rnn_states, self.rnn_states_critic, self.masks, self.bad_masks):
