@@ -636,6 +636,52 @@ int mappo_rollout_episode_adversary(const mappo_comm_agent *agents /*host, [3]*/
                                     int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                                     int32_t centralized, mappo_stream_t stream);
 
+/* GPU-vectorised MPE simple_tag, predator-prey (csrc/mpe_tag_env.hip, device functions in csrc/mpe_tag_core.h): N environments of
+ * the fixed shape num_adversaries = 3, num_good_agents = 1, num_landmarks = 2 (num_agents = 4) — agents 0..2 the ADVERSARIES (size
+ * 0.075, accel 3, max_speed 1), agent 3 the GOOD agent (size 0.05, accel 4, max_speed 1.3), landmarks of size 0.2 that collide and
+ * do not move; every agent moves, Discrete(5); nobody speaks — one launch per step.  Observation of agent m: own velocity 2, own
+ * position 2, the 2 landmarks relative to it 4, the three other agents relative to it in world-agent order 6, and for an adversary
+ * the good agent's velocity 2: 16 | 16 | 16 | 14 features.  Replaces MultiAgentEnv.step / _set_action (environment.py:117-256:
+ * u = (a1 - a2, a3 - a4) * accel), World.step (core.py:207-322: action force accel * u — accel a second time —, the soft-collision
+ * force between every pair of entities of which one can move, dist_min the two sizes added, pairs a < b over agents then landmarks;
+ * damping 0.25; the max_speed clamp; dt 0.1; mass 1), Scenario.reset_world / reward / observation (scenarios/simple_tag.py:37-144) +
+ * the vec-env's reset-on-done (env_wrappers.py:146-152).  State is caller-owned device memory: agent_pos / agent_vel [N][4][2] and
+ * landmark_pos [N][2][2] in float64, tstep [N] int32, episode [N] int64 (reset counter = Philox counter).  Outputs: obs_adv0 /
+ * obs_adv1 / obs_adv2 [N][16], obs_good [N][14] fp32; rewards [N][4] fp32, ONE PER AGENT and never summed (world.collaborative is not
+ * set, environment.py:49-50,142): every adversary 10 x (adversaries within 0.125 of the good agent), the good agent the negative of
+ * that minus the boundary penalty of |x| and of |y| (0 below 0.9, 10 (x - 0.9) below 1, else min(exp(2 x - 2), 10)); dones [N][4]
+ * bool bytes.  action_mode 0: the reference's one-hots / probabilities, actions [N][4][5]; 1: indices as fp32, actions [N][4],
+ * clamped to 0..4 (1/2/3/4 = +x/-x/+y/-y).  Physics in float64 with contraction off; the contact force and the penalty go through
+ * the device's exp / log1p, so obs and rewards match the fp32 cast of the reference's float64 values to 1e-6 rather than to the
+ * bit.  An environment whose episode ends (tstep >= episode_length) is reset inside the same launch and returns the reset
+ * observation.  Reset draws: Philox stream (seed, episode), 64-bit uniform number 16 n + k of environment n — k = 2 a, 2 a + 1:
+ * position of agent a in U(-1,1); k = 8 + 2 l, 9 + 2 l: position of landmark l in 0.8 U(-1,1); k = 12..15 unused; velocities start
+ * at zero.  Both validate on the host and name the fault: num_agents == 4 (the only shape built), N >= 1, non-null pointers,
+ * action_mode 0 or 1, episode_length >= 1. */
+int mappo_mpe_tag_reset(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *tstep, int64_t *episode,
+                        float *obs_adv0, float *obs_adv1, float *obs_adv2, float *obs_good, int32_t N, int32_t num_agents,
+                        uint64_t seed, mappo_stream_t stream);
+int mappo_mpe_tag_step(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *tstep, int64_t *episode,
+                       const float *actions, int32_t action_mode, float *obs_adv0, float *obs_adv1, float *obs_adv2,
+                       float *obs_good, float *rewards, uint8_t *dones, int32_t N, int32_t num_agents, int32_t episode_length,
+                       uint64_t seed, mappo_stream_t stream);
+/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner (csrc/rollout_tag.h): what
+ * T x (one mappo_rollout_step per agent + mappo_mpe_tag_step with action_mode 1 + the agents' inserts) + one bootstrap
+ * mappo_rollout_step per agent do, bit for bit.  agents: four mappo_comm_agent (adversaries 0, 1, 2, then the good agent).  Per step
+ * t < T: agent m's actor on its observation rows of step t (step 0: obs_buf slot 0), row n sampled with (agent's seed, counter + t
+ * (+ the agent's *counter_dev), Philox index n) -> actions / logp slot t; the environments step in float64 on the sampled indices
+ * (reset-on-done after env_episode_length steps); each agent's observation -> its obs_buf slot t + 1, its share row (centralized:
+ * the four observations side by side, 16 | 16 | 16 | 14 = 62; else its own observation) -> share_buf slot t + 1, its OWN reward ->
+ * rew_buf slot t, 1 - done -> mask_buf slot t + 1.  Each critic on its share rows of step t <= T -> values, step T -> next_values.
+ * The five state arrays are stored back at the end, so the environment continues in either path.  Host checks, each named in the
+ * error: non-null descriptors; not recurrent; layer_N <= 1; actors in 16 / 16 / 16 / 14 and out 5; critics out 1 and in 62
+ * (centralized) or the agent's own in_dim; the same layer_N and activation in all eight networks; T, N, env_episode_length >= 1;
+ * non-null pointers. */
+int mappo_rollout_episode_tag(const mappo_comm_agent *agents /*host, [4]*/, double *agent_pos, double *agent_vel,
+                              double *landmark_pos, int32_t *tstep, int64_t *episode, int32_t T, int32_t N,
+                              int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
+                              int32_t centralized, mappo_stream_t stream);
+
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only
  * produces data of the SMAC shapes with agents that die and episodes that end.  obs [N][M][D], share_obs [N][M][S] ~ N(0,1);

@@ -1,2 +1,3 @@
 from .mpe_speaker_listener import SimpleSpeakerListenerVecEnv  # noqa: F401
 from .mpe_adversary import SimpleAdversaryVecEnv  # noqa: F401
+from .mpe_tag import SimpleTagVecEnv  # noqa: F401

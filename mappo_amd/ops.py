@@ -435,6 +435,22 @@ def rollout_episode_adversary(agents, T, N, env_episode_length, env_seed, agent_
     _lib.check(rc, "mappo_rollout_episode_adversary")
 
 
+def rollout_episode_tag(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, tstep, episode, deterministic,
+                        counter, centralized):
+    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_tag env in one launch, env steps included
+    (mappo_rollout_episode_tag).  agents: the four comm_agent(...) of agents 0 .. 2 (adversaries) and 3 (good); the five env state
+    tensors (SimpleTagVecEnv) are read, stepped T times on the sampled indices and stored back."""
+    if len(agents) != 4:
+        raise ValueError(f"rollout_episode_tag: simple_tag is built for num_agents = 4 (got {len(agents)} agents)")
+    f64 = torch.float64
+    arr = (_lib.CommAgent * 4)(*agents)
+    rc = _lib.load().mappo_rollout_episode_tag(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
+                                               _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T), int(N), int(env_episode_length),
+                                               int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)), int(counter) & (2 ** 64 - 1),
+                                               int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode_tag")
+
+
 def mlp_backward_slabs(B):
     return int(_lib.load().mappo_mlp_backward_slabs(int(B)))
 
@@ -817,6 +833,33 @@ def mpe_adversary_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
                                               _ptr(obs_adversary), _ptr(obs_good1), _ptr(obs_good2), _ptr(rewards), _ptr(dones, torch.uint8),
                                               int(N), int(num_agents), int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
     _lib.check(rc, "mappo_mpe_adversary_step")
+
+
+# ---- GPU-vectorised MPE simple_tag (csrc/mpe_tag_env.hip): three adversaries + one good agent, Discrete(5) each, per-agent rewards ------
+def _tag_agents(who, num_agents):
+    if int(num_agents) != 4:
+        raise ValueError(f"{who}: simple_tag is built for num_agents = 4: 3 adversaries, 1 good agent, 2 landmarks (got {num_agents})")
+
+
+def mpe_tag_reset(agent_pos, agent_vel, landmark_pos, tstep, episode, obs_adv0, obs_adv1, obs_adv2, obs_good, N, seed, num_agents=4):
+    _tag_agents("mpe_tag_reset", num_agents)
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_tag_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
+                                         _ptr(episode, torch.int64), _ptr(obs_adv0), _ptr(obs_adv1), _ptr(obs_adv2), _ptr(obs_good), int(N),
+                                         int(num_agents), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_tag_reset")
+
+
+def mpe_tag_step(agent_pos, agent_vel, landmark_pos, tstep, episode, actions, action_mode, obs_adv0, obs_adv1, obs_adv2, obs_good, rewards,
+                 dones, N, episode_length, seed, num_agents=4):
+    """action_mode 0: one-hots [N, 4, 5] | 1: fp32 indices [N, 4].  rewards [N, 4]: one per agent."""
+    _tag_agents("mpe_tag_step", num_agents)
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_tag_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
+                                        _ptr(episode, torch.int64), _ptr(actions), int(action_mode), _ptr(obs_adv0), _ptr(obs_adv1),
+                                        _ptr(obs_adv2), _ptr(obs_good), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(num_agents),
+                                        int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_tag_step")
 
 
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):

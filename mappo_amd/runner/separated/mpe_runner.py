@@ -12,7 +12,9 @@ collect through mappo_rollout_step (one launch per agent for actor + critic), an
 whole episode — both agents' networks, the env steps and the inserts — is ONE launch (mappo_rollout_episode_comm) with the same
 buffer contents and env state, bit for bit; MAPPO_COMM_EPISODE=0 keeps the stepwise path (A/B runs, tests).  The GPU-resident
 simple_adversary env (three agents, observations of 8 / 10 / 10 features, per-agent rewards) runs the same two ways:
-mappo_rollout_episode_adversary, MAPPO_ADV_EPISODE=0 for the stepwise path."""
+mappo_rollout_episode_adversary, MAPPO_ADV_EPISODE=0 for the stepwise path.  The GPU-resident simple_tag env (four agents,
+observations of 16 / 16 / 16 / 14 features, per-agent rewards) likewise: mappo_rollout_episode_tag, MAPPO_TAG_EPISODE=0 for the
+stepwise path."""
 import os
 import time
 
@@ -74,6 +76,9 @@ class MPERunner(Runner):
             return infos
         if self._adversary_episode_ready():
             self._collect_episode_adversary(deterministic)
+            return infos
+        if self._tag_episode_ready():
+            self._collect_episode_tag(deterministic)
             return infos
         for step in range(self.episode_length):
             values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env = self.collect(step, deterministic)
@@ -212,6 +217,33 @@ class MPERunner(Runner):
                for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer))]
         ops.rollout_episode_adversary(ags, self.episode_length, N, st["T"], st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"],
                                       st["goal"], st["tstep"], st["episode"], deterministic, 0, self.use_centralized_V)
+        for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
+            b.step = 0
+            tr.prep_rollout()
+            b.compute_returns(self._next_values[agent_id], tr.value_normalizer)
+
+    # ---- the same on simple_tag (mappo_rollout_episode_tag) ----
+    def _tag_episode_ready(self):
+        """The env is the GPU-resident simple_tag and the four policies are what the kernel is built for; anything else takes the
+        stepwise path."""
+        env = self.envs
+        if os.environ.get("MAPPO_TAG_EPISODE", "1") == "0" or not hasattr(env, "episode_state_tag") or self.num_agents != 4:
+            return False
+        return self._episode_shapes_ready(env, env.agent_pos.device)
+
+    @torch.no_grad()
+    def _collect_episode_tag(self, deterministic=False):
+        """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent."""
+        st = self.envs.episode_state_tag()
+        N = self.n_rollout_threads
+        if self._next_values is None:
+            self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
+        from mappo_amd import ops
+        ags = [ops.comm_agent(p.actor.flat, p.actor.desc, p.critic.flat, p.critic.desc, p.actor._seed, p.actor._counter_dev, b.obs, b.share_obs,
+                              b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds, self._next_values[agent_id])
+               for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer))]
+        ops.rollout_episode_tag(ags, self.episode_length, N, st["T"], st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"],
+                                st["tstep"], st["episode"], deterministic, 0, self.use_centralized_V)
         for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
             b.step = 0
             tr.prep_rollout()
