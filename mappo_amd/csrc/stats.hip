@@ -110,14 +110,12 @@ extern "C" int mappo_minibatch_moments(const float *returns, const float *active
   return MAPPO_OK;
 }
 
-// valuenorm.py:37-54: running <- running*w + batch*(1-w); each product/sum rounded to fp32 like torch.
+// valuenorm.py:37-54: running <- running*w + batch*(1-w), the step of stats_core.h (bit-equal to one trip of valuenorm_update_n).
 __global__ void valuenorm_update_kernel(float *vn_state, const double *mb_moments, float w, float omw) {
-  const double B = mb_moments[3] > 0.0 ? mb_moments[3] : 1.0;
-  const float bm = (float)(mb_moments[0] / B);
-  const float bsq = (float)(mb_moments[1] / B);
-  vn_state[0] = __fadd_rn(__fmul_rn(vn_state[0], w), __fmul_rn(bm, omw));
-  vn_state[1] = __fadd_rn(__fmul_rn(vn_state[1], w), __fmul_rn(bsq, omw));
-  vn_state[2] = __fadd_rn(__fmul_rn(vn_state[2], w), omw);
+  const VnBatchTerms t = valuenorm_batch_terms(mb_moments[0], mb_moments[1], mb_moments[3], omw);
+  float s0 = vn_state[0], s1 = vn_state[1], s2 = vn_state[2];
+  valuenorm_ema_step(s0, s1, s2, t, w, omw);
+  vn_state[0] = s0; vn_state[1] = s1; vn_state[2] = s2;
 }
 
 extern "C" int mappo_valuenorm_update(float *vn_state, const double *mb_moments, double beta, mappo_stream_t stream) {

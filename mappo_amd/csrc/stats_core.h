@@ -45,18 +45,35 @@ __device__ __forceinline__ void minibatch_moments_term(float r, float active, do
   v[2] += (double)active;
 }
 
-// valuenorm.py:37-54, n times with the same batch moments {m0 = sum ret, m1 = sum ret^2, m3 = B}:
-// running <- running*w + batch*(1-w); each product/sum rounded to fp32 like torch.  One thread.
+// valuenorm.py:37-54, one EMA step: running <- running*w + batch*(1-w).  The batch term is rounded to fp32 once and the
+// running term enters through one fused multiply-add, spelled out so that the compiler has no choice of which product to
+// fuse: valuenorm_update_kernel, valuenorm_update_n_kernel and the fused prologue all take this step and agree bit for bit.
+// (Left to contraction -- __fmul_rn / __fadd_rn do not stop it -- the single update fused the batch product, the loop, its
+// invariant product hoisted, the running one, and the two differed in the last bit.)
+struct VnBatchTerms { float b0, b1; };   // batch mean * (1-w), batch mean of squares * (1-w)
+
+__device__ __forceinline__ VnBatchTerms valuenorm_batch_terms(double m0, double m1, double m3, float omw) {
+#pragma clang fp contract(off)
+  const double B = m3 > 0.0 ? m3 : 1.0;
+  VnBatchTerms t;
+  t.b0 = (float)(m0 / B) * omw;
+  t.b1 = (float)(m1 / B) * omw;
+  return t;
+}
+
+__device__ __forceinline__ void valuenorm_ema_step(float &s0, float &s1, float &s2, const VnBatchTerms &t, float w, float omw) {
+  s0 = __fmaf_rn(s0, w, t.b0);
+  s1 = __fmaf_rn(s1, w, t.b1);
+  s2 = __fmaf_rn(s2, w, omw);
+}
+
+// n such steps with the same batch moments {m0 = sum ret, m1 = sum ret^2, m3 = B}.  One thread.
 __device__ __forceinline__ void valuenorm_update_n_body(float *vn_state, double m0, double m1, double m3, float w, float omw, int n,
                                                         float *states_out) {
-  const double B = m3 > 0.0 ? m3 : 1.0;
-  const float bm = (float)(m0 / B);
-  const float bsq = (float)(m1 / B);
+  const VnBatchTerms t = valuenorm_batch_terms(m0, m1, m3, omw);
   float s0 = vn_state[0], s1 = vn_state[1], s2 = vn_state[2];
   for (int e = 0; e < n; ++e) {
-    s0 = __fadd_rn(__fmul_rn(s0, w), __fmul_rn(bm, omw));
-    s1 = __fadd_rn(__fmul_rn(s1, w), __fmul_rn(bsq, omw));
-    s2 = __fadd_rn(__fmul_rn(s2, w), omw);
+    valuenorm_ema_step(s0, s1, s2, t, w, omw);
     states_out[3 * e + 0] = s0; states_out[3 * e + 1] = s1; states_out[3 * e + 2] = s2;
   }
   vn_state[0] = s0; vn_state[1] = s1; vn_state[2] = s2;

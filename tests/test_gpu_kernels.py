@@ -76,7 +76,8 @@ def test_gae_golden_all_branches(ops):
 
 @pytest.mark.parametrize("T,N,M", [(25, 1024, 3), (400, 64, 3), (1100, 5, 3), (1, 3, 2), (33, 7, 1)])
 def test_gae_vs_oracle_sizes(ops, T, N, M):
-    """BASELINE config-2 size, SMAC-length episodes, the multi-chunk path (T > 512), ragged R."""
+    """BASELINE config-2 size, SMAC-length episodes, the multi-chunk path (a chunk is 256 steps: T = 400 takes two, T = 1100
+    five), ragged R."""
     rng = np.random.default_rng(T * 1000 + N)
     f = np.float32
     rewards = rng.standard_normal((T, N, M, 1)).astype(f)
