@@ -43,6 +43,23 @@ def test_bad_arguments_return_error_codes_not_crashes():
     assert rc == -1 and b"hidden_size" in lib.mappo_last_error()
 
 
+def test_recurrent_rows_rejects_bad_arguments_before_any_launch():
+    """mappo_recurrent_rows: fewer chunks than minibatches (mbs would be 0) and a buffer whose T * R rows do not fit the
+    int32 row indices both return MAPPO_EINVAL with a message; the checks come before the launch, so no GPU is needed."""
+    from mappo_amd import _lib
+    lib = _lib.load()
+    fake = ctypes.c_void_p(4096)                          # non-NULL, never dereferenced
+    # (perm, n_epochs, data_chunks, L, T, R, num_mini_batch, rows, h0_rows, stream)
+    assert lib.mappo_recurrent_rows(fake, 1, 3, 10, 10, 3, 4, fake, fake, None) == -1
+    assert b"fewer chunks than minibatches" in lib.mappo_last_error()
+    assert lib.mappo_recurrent_rows(fake, 1, 4, 1, 65536, 32768, 2, fake, fake, None) == -1          # T * R = 2^31
+    assert b"exceed int32" in lib.mappo_last_error()
+    assert lib.mappo_recurrent_rows(fake, 1, 4, 1, 2 ** 31 - 1, 2 ** 31 - 1, 2, fake, fake, None) == -1
+    assert b"exceed int32" in lib.mappo_last_error()
+    assert lib.mappo_recurrent_rows(None, 1, 4, 1, 4, 1, 2, fake, fake, None) == -1
+    assert b"recurrent_rows: bad arguments" in lib.mappo_last_error()
+
+
 def test_wide_entry_points_reject_bad_arguments_and_layout_is_a_pure_function():
     """mappo_wide_layout / mappo_wide_l1_backward (include/mappo_hip.h): argument validation happens before any launch, so the
     error paths run without a GPU.  The layout a producer leaves is a function of (descriptor, producer) only — no host state."""

@@ -122,6 +122,50 @@ def test_insert_after_update():
         np.testing.assert_array_equal(getattr(buf, n), g["final/" + n])
 
 
+def test_insert_ref_matches_golden_slots():
+    """tests/insert_ref.py, the NumPy reference of test_gpu_insert_matrix.py, against the buffer the reference filled: every
+    insert of golden/insert.npz (the step wraps after T) lands in the slot the reference wrote, with the reference's values.
+    The fixture's masks are drawn per agent, so they pin insert_mpe_ref's mask (dones := masks == 0) and state reset; its
+    share_obs, available_actions and bad_masks pin insert_smac_ref's copies and bad mask."""
+    from insert_ref import episode_insert_ref, insert_mpe_ref, insert_smac_ref
+    g = golden("insert")
+    T, N, M = 4, 2, 3
+    assert int(g["n_inserts"]) == T + 2
+    steps = []
+    for s in range(T + 2):
+        d = sub(g, f"in{s}")
+        step, snap = s % T, ("full/" if s < T else "final/")
+        dones = d["masks"][..., 0] == 0
+        rnn = (d["rnn_a"].reshape(N * M, 1, 8), d["rnn_c"].reshape(N * M, 1, 8))
+        obs, share, rew, mask, ha, hc = insert_mpe_ref(d["obs"], d["rewards"], dones, False, rnn)
+        np.testing.assert_array_equal(obs, g[snap + "obs"][step + 1])
+        np.testing.assert_array_equal(share, g[snap + "obs"][step + 1])
+        np.testing.assert_array_equal(rew, g[snap + "rewards"][step])
+        np.testing.assert_array_equal(mask, g[snap + "masks"][step + 1])
+        for got, name in ((ha, "rnn_states"), (hc, "rnn_states_critic")):
+            want = g[snap + name][step + 1].reshape(N * M, 1, 8)
+            keep = ~dones.reshape(N * M)
+            np.testing.assert_array_equal(got[keep], want[keep])
+            assert (got[~keep] == 0).all() and (want[~keep] != 0).all()
+        cen = insert_mpe_ref(d["obs"], d["rewards"][..., 0], dones, True)
+        assert cen[1].shape == (N, M, M * 6)
+        for m in range(M):
+            np.testing.assert_array_equal(cen[1][:, m], g[snap + "obs"][step + 1].reshape(N, M * 6))
+        for a, b in zip(cen[:1] + cen[2:], (obs, rew, mask)):
+            np.testing.assert_array_equal(a, b)
+        out = insert_smac_ref(d["obs"], d["share_obs"], d["avail"], d["rewards"], np.zeros((N, M), dtype=bool), d["bad"][..., 0] == 0, rnn)
+        names = ("obs", "share_obs", "available_actions", "rewards", "masks", "bad_masks", "active_masks", "rnn_states", "rnn_states_critic")
+        for got, name in zip(out, names):
+            lo = step if name == "rewards" else step + 1
+            want = np.ones((N, M, 1), np.float32) if name in ("masks", "active_masks") else g[snap + name][lo]
+            np.testing.assert_array_equal(got.reshape(want.shape), want, err_msg=name)
+        if s < T:
+            steps.append((d["obs"], d["rewards"], dones))
+    ep = episode_insert_ref(*(np.stack(x) for x in zip(*steps)), False)
+    for got, name, lo in zip(ep, ("obs", "obs", "rewards", "masks"), (1, 1, 0, 1)):
+        np.testing.assert_array_equal(got, g["full/" + name][lo:lo + T])
+
+
 def test_forward_paths():
     g = golden("forward")
     t = torch.from_numpy
