@@ -34,15 +34,7 @@
 #include "mpe_adv_core.h"
 #include "rollout_comm.h"
 
-struct AdvEpisodeArgs {
-  CommNet a[MPE_ADV_M], c[MPE_ADV_M];            // per agent (0: adversary, 1 and 2: good agents)
-  MpeAdvArgs env;                                // state arrays, N, T = the ENV's episode length, mode 1, seed
-  float *obs_buf[MPE_ADV_M], *share_buf[MPE_ADV_M];        // [T + 1][N][D_m], [T + 1][N][S_m]
-  float *rew_buf[MPE_ADV_M], *mask_buf[MPE_ADV_M];         // [T][N], [T + 1][N]
-  float *next_values[MPE_ADV_M];                 // [N]: the critic at step T
-  uint64_t counter;
-  int T, centralized, deterministic;             // rollout steps
-};
+typedef SepEpisodeArgs<MpeAdvArgs, MPE_ADV_M> AdvEpisodeArgs;         // agent 0: adversary, 1 and 2: good agents
 
 #define ADV_EP_G 16                                                 // environments per tile (workgroup)
 #define ADV_EP_WAVES 4
@@ -141,68 +133,26 @@ __global__ __launch_bounds__(ADV_EP_WAVES * WAVE, 1) void rollout_episode_advers
   }
 }
 
-template <bool R, int L>
-static int adv_episode_launch(dim3 grid, hipStream_t st, const AdvEpisodeArgs &a) {
-  const size_t lds_bytes = sizeof(float) * adv_ep_lds_floats<L>();
-  static const hipError_t e_ = hipFuncSetAttribute((const void *)rollout_episode_adversary_kernel<R, L>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)(sizeof(float) * adv_ep_lds_floats<L>()));
-  if (e_ != hipSuccess) { mappo_set_error("rollout_episode_adversary: hipFuncSetAttribute: %s", hipGetErrorString(e_)); (void)hipGetLastError(); return MAPPO_ELAUNCH; }
-  hipLaunchKernelGGL((rollout_episode_adversary_kernel<R, L>), grid, dim3(ADV_EP_WAVES * WAVE), lds_bytes, st, a);
-  return MAPPO_OK;
-}
-
 extern "C" int mappo_rollout_episode_adversary(const mappo_comm_agent *agents, double *agent_pos, double *agent_vel, double *landmark_pos,
                                                int32_t *goal, int32_t *tstep, int64_t *episode, int32_t T, int32_t N,
                                                int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                                                int32_t centralized, mappo_stream_t stream) {
   const char *who = "rollout_episode_adversary";
   MAPPO_REQUIRE(agents, "%s: null agent descriptors (needs num_agents = 3 of them: adversary, good agent 1, good agent 2)", who);
-  const char *name[MPE_ADV_M] = {"adversary", "good agent 1", "good agent 2"};
-  for (int m = 0; m < MPE_ADV_M; ++m) {
-    const mappo_net_desc &da = agents[m].actor_desc, &dc = agents[m].critic_desc;
-    const int D = mpe_adv_obs_dim(m);
-    MAPPO_REQUIRE(!da.recurrent && !dc.recurrent, "%s: %s: recurrent networks take the stepwise path (this launch is feed-forward only)", who,
-                  name[m]);
-    MAPPO_REQUIRE(da.layer_N >= 0 && da.layer_N <= 1, "%s: %s: layer_N %d: this launch takes layer_N <= 1", who, name[m], da.layer_N);
-    if (int rc = check_desc(&da, who)) return rc;
-    if (int rc = check_desc(&dc, who)) return rc;
-    MAPPO_REQUIRE(da.in_dim == D && da.out_dim == MPE_ADV_U, "%s: %s actor in_dim %d / out_dim %d: simple_adversary has in_dim %d and %d "
-                  "actions there", who, name[m], da.in_dim, da.out_dim, D, MPE_ADV_U);
-    MAPPO_REQUIRE(dc.out_dim == 1, "%s: %s critic out_dim must be 1", who, name[m]);
-    if (centralized)
-      MAPPO_REQUIRE(dc.in_dim == MPE_ADV_SHARE, "%s: %s: centralized critic needs in_dim 8 + 10 + 10 = %d (got %d)", who, name[m],
-                    MPE_ADV_SHARE, dc.in_dim);
-    else
-      MAPPO_REQUIRE(dc.in_dim == D, "%s: %s critic in_dim %d != actor in_dim %d", who, name[m], dc.in_dim, D);
-    MAPPO_REQUIRE(da.layer_N == agents[0].actor_desc.layer_N && dc.layer_N == da.layer_N && da.use_relu == agents[0].actor_desc.use_relu &&
-                  dc.use_relu == da.use_relu, "%s: all six networks must share layer_N and the activation", who);
-  }
-  MAPPO_REQUIRE(T >= 1 && N >= 1 && env_episode_length >= 1, "%s: bad shape T=%d N=%d env episode length %d (each needs >= 1)", who, T, N,
-                env_episode_length);
+  const char *const name[MPE_ADV_M] = {"adversary", "good agent 1", "good agent 2"};
+  const int Dm[MPE_ADV_M] = {MPE_ADV_OBS_A, MPE_ADV_OBS_G, MPE_ADV_OBS_G}, Am[MPE_ADV_M] = {MPE_ADV_U, MPE_ADV_U, MPE_ADV_U};
+  AdvEpisodeArgs e;
+  if (int rc = sep_episode_fill(e, who, agents, name, Dm, Am, MPE_ADV_SHARE, centralized, deterministic, counter, T, N, env_episode_length)) return rc;
   MAPPO_REQUIRE(agent_pos && agent_vel && landmark_pos && goal && tstep && episode, "%s: bad arguments (null state pointer)", who);
-  for (int m = 0; m < MPE_ADV_M; ++m)
-    MAPPO_REQUIRE(agents[m].actor_params && agents[m].critic_params && agents[m].obs_buf && agents[m].share_buf && agents[m].rew_buf &&
-                  agents[m].mask_buf && agents[m].actions && agents[m].logp && agents[m].values && agents[m].next_values,
-                  "%s: bad arguments (null pointer, %s)", who, name[m]);
   MAPPO_CLEAR_STICKY();
-  AdvEpisodeArgs e = {};
-  for (int m = 0; m < MPE_ADV_M; ++m) {
-    const mappo_comm_agent &ag = agents[m];
-    e.a[m].params = ag.actor_params; e.a[m].actions = ag.actions; e.a[m].logp = ag.logp; e.a[m].desc = ag.actor_desc;
-    e.a[m].off = net_offsets(e.a[m].desc); e.a[m].seed = ag.seed; e.a[m].counter_dev = ag.counter_dev;
-    e.c[m].params = ag.critic_params; e.c[m].out = ag.values; e.c[m].desc = ag.critic_desc; e.c[m].off = net_offsets(e.c[m].desc);
-    e.obs_buf[m] = ag.obs_buf; e.share_buf[m] = ag.share_buf; e.rew_buf[m] = ag.rew_buf; e.mask_buf[m] = ag.mask_buf;
-    e.next_values[m] = ag.next_values;
-  }
   e.env.apos = agent_pos; e.env.avel = agent_vel; e.env.lpos = landmark_pos; e.env.goal = goal; e.env.tstep = tstep; e.env.episode = episode;
   e.env.N = N; e.env.T = env_episode_length; e.env.mode = 1; e.env.seed = env_seed;
-  e.counter = counter; e.T = T; e.centralized = centralized; e.deterministic = deterministic;
   const dim3 grid((unsigned)((N + ADV_EP_G - 1) / ADV_EP_G));
-  const bool relu = agents[0].actor_desc.use_relu != 0;
-  int rc;
-  if (agents[0].actor_desc.layer_N == 0) rc = relu ? adv_episode_launch<true, 0>(grid, as_stream(stream), e) : adv_episode_launch<false, 0>(grid, as_stream(stream), e);
-  else rc = relu ? adv_episode_launch<true, 1>(grid, as_stream(stream), e) : adv_episode_launch<false, 1>(grid, as_stream(stream), e);
-  if (rc) return rc;
-  MAPPO_CHECK_LAUNCH("rollout_episode_adversary");
+  if (int rc = dispatch_relu_ln<1>(agents[0].actor_desc.use_relu != 0, agents[0].actor_desc.layer_N, [&](auto R, auto L) {
+        constexpr int lds_bytes = sizeof(float) * adv_ep_lds_floats<L.value>();
+        return launch_kernel<rollout_episode_adversary_kernel<R.value, L.value>, lds_bytes>(who, grid, dim3(ADV_EP_WAVES * WAVE), lds_bytes, as_stream(stream), e);
+      }))
+    return rc;
+  MAPPO_CHECK_LAUNCH(who);
   return MAPPO_OK;
 }

@@ -27,37 +27,14 @@
 // state end up bit-identical to the stepwise path's.
 #pragma once
 #include "mpe_comm_core.h"
-#include "rollout_spread.h"
+#include "rollout_separated.h"
 
-struct CommNet {                   // what tile16r_step reads of a FwdArgs, per network (four FwdArgs would not fit the kernel arguments)
-  const float *params;
-  float *out, *actions, *logp;     // critic: values [T][N] | actor: actions / logp [T][N]
-  mappo_net_desc desc;
-  NetOff off;
-  uint64_t seed;
-  const uint64_t *counter_dev;     // actor: the agent's own device word added to the counter (may be null)
-};
-
-struct CommEpisodeArgs {
-  CommNet a[MPE_COMM_M], c[MPE_COMM_M];          // per agent (0: speaker, 1: listener)
-  MpeCommArgs env;                               // state arrays, N, T = the ENV's episode length, mode 1, seed
-  float *obs_buf[MPE_COMM_M], *share_buf[MPE_COMM_M];      // [T + 1][N][D_m], [T + 1][N][S_m]
-  float *rew_buf[MPE_COMM_M], *mask_buf[MPE_COMM_M];       // [T][N], [T + 1][N]
-  float *next_values[MPE_COMM_M];                // [N]: the critic at step T
-  uint64_t counter;
-  int T, centralized, deterministic;             // rollout steps
-};
+typedef SepEpisodeArgs<MpeCommArgs, MPE_COMM_M> CommEpisodeArgs;     // agent 0: speaker, 1: listener
 
 #define COMM_EP_G 16                                                // environments per tile (workgroup)
 #define COMM_EP_WAVES 4
 #define COMM_X_TILE (16 * MPE_COMM_SHARE)
 #define COMM_EP_LDS_FLOATS (COMM_X_TILE + 2 * 16 * TP + 2 * 16)     // observation tile | two logits tiles | action tile
-
-__device__ __forceinline__ void comm_fwd_args(FwdArgs &f, const CommNet &n, int64_t B, int deterministic) {
-  f = FwdArgs{};
-  f.params = n.params; f.out = n.out; f.actions = n.actions; f.logp = n.logp; f.desc = n.desc; f.off = n.off; f.B = B;
-  f.deterministic = deterministic; f.seed = n.seed;
-}
 
 template <bool RELU, int LN>
 __global__ __launch_bounds__(COMM_EP_WAVES * WAVE, 1) void rollout_episode_comm_kernel(CommEpisodeArgs e) {
@@ -141,12 +118,6 @@ __global__ __launch_bounds__(COMM_EP_WAVES * WAVE, 1) void rollout_episode_comm_
   }
 }
 
-template <bool R, int L>
-static int comm_episode_launch(dim3 grid, size_t lds_bytes, hipStream_t st, const CommEpisodeArgs &a) {
-  hipLaunchKernelGGL((rollout_episode_comm_kernel<R, L>), grid, dim3(COMM_EP_WAVES * WAVE), lds_bytes, st, a);
-  return MAPPO_OK;
-}
-
 extern "C" int mappo_rollout_episode_comm(const mappo_comm_agent *speaker, const mappo_comm_agent *listener, int32_t T, int32_t N,
                                           int32_t env_episode_length, uint64_t env_seed, double *listener_pos, double *listener_vel,
                                           double *landmark_pos, int32_t *goal, int32_t *symbol, int32_t *tstep, int64_t *episode,
@@ -154,52 +125,21 @@ extern "C" int mappo_rollout_episode_comm(const mappo_comm_agent *speaker, const
                                           mappo_stream_t stream) {
   const char *who = "rollout_episode_comm";
   MAPPO_REQUIRE(speaker && listener, "%s: null agent descriptor", who);
-  const mappo_comm_agent *ag[MPE_COMM_M] = {speaker, listener};
+  const mappo_comm_agent ag[MPE_COMM_M] = {*speaker, *listener};
+  const char *const name[MPE_COMM_M] = {"speaker", "listener"};
   const int Dm[MPE_COMM_M] = {MPE_COMM_OBS_S, MPE_COMM_OBS_L}, Am[MPE_COMM_M] = {MPE_COMM_C, MPE_COMM_U};
-  const char *name[MPE_COMM_M] = {"speaker", "listener"};
-  for (int m = 0; m < MPE_COMM_M; ++m) {
-    const mappo_net_desc &da = ag[m]->actor_desc, &dc = ag[m]->critic_desc;
-    MAPPO_REQUIRE(!da.recurrent && !dc.recurrent, "%s: %s: recurrent networks take the stepwise path (this launch is feed-forward only)", who,
-                  name[m]);
-    MAPPO_REQUIRE(da.layer_N >= 0 && da.layer_N <= 1, "%s: %s: layer_N %d: this launch takes layer_N <= 1", who, name[m], da.layer_N);
-    if (int rc = check_desc(&da, who)) return rc;
-    if (int rc = check_desc(&dc, who)) return rc;
-    MAPPO_REQUIRE(da.in_dim == Dm[m] && da.out_dim == Am[m], "%s: %s actor in_dim %d / out_dim %d: simple_speaker_listener has in_dim %d and "
-                  "%d actions there", who, name[m], da.in_dim, da.out_dim, Dm[m], Am[m]);
-    MAPPO_REQUIRE(dc.out_dim == 1, "%s: %s critic out_dim must be 1", who, name[m]);
-    if (centralized)
-      MAPPO_REQUIRE(dc.in_dim == MPE_COMM_SHARE, "%s: %s: centralized critic needs in_dim 3 + 11 = %d (got %d)", who, name[m], MPE_COMM_SHARE,
-                    dc.in_dim);
-    else
-      MAPPO_REQUIRE(dc.in_dim == Dm[m], "%s: %s critic in_dim %d != actor in_dim %d", who, name[m], dc.in_dim, Dm[m]);
-    MAPPO_REQUIRE(da.layer_N == speaker->actor_desc.layer_N && dc.layer_N == da.layer_N && da.use_relu == speaker->actor_desc.use_relu &&
-                  dc.use_relu == da.use_relu, "%s: all four networks must share layer_N and the activation", who);
-  }
-  MAPPO_REQUIRE(T >= 1 && N >= 1 && env_episode_length >= 1, "%s: bad shape T=%d N=%d env episode length %d (each needs >= 1)", who, T, N,
-                env_episode_length);
+  CommEpisodeArgs e;
+  if (int rc = sep_episode_fill(e, who, ag, name, Dm, Am, MPE_COMM_SHARE, centralized, deterministic, counter, T, N, env_episode_length)) return rc;
   MAPPO_REQUIRE(listener_pos && listener_vel && landmark_pos && goal && symbol && tstep && episode, "%s: bad arguments (null state pointer)", who);
-  for (int m = 0; m < MPE_COMM_M; ++m)
-    MAPPO_REQUIRE(ag[m]->actor_params && ag[m]->critic_params && ag[m]->obs_buf && ag[m]->share_buf && ag[m]->rew_buf && ag[m]->mask_buf &&
-                  ag[m]->actions && ag[m]->logp && ag[m]->values && ag[m]->next_values, "%s: bad arguments (null pointer, %s)", who, name[m]);
   MAPPO_CLEAR_STICKY();
-  CommEpisodeArgs e = {};
-  for (int m = 0; m < MPE_COMM_M; ++m) {
-    e.a[m].params = ag[m]->actor_params; e.a[m].actions = ag[m]->actions; e.a[m].logp = ag[m]->logp; e.a[m].desc = ag[m]->actor_desc;
-    e.a[m].off = net_offsets(e.a[m].desc); e.a[m].seed = ag[m]->seed; e.a[m].counter_dev = ag[m]->counter_dev;
-    e.c[m].params = ag[m]->critic_params; e.c[m].out = ag[m]->values; e.c[m].desc = ag[m]->critic_desc; e.c[m].off = net_offsets(e.c[m].desc);
-    e.obs_buf[m] = ag[m]->obs_buf; e.share_buf[m] = ag[m]->share_buf; e.rew_buf[m] = ag[m]->rew_buf; e.mask_buf[m] = ag[m]->mask_buf;
-    e.next_values[m] = ag[m]->next_values;
-  }
   e.env.pos = listener_pos; e.env.vel = listener_vel; e.env.lpos = landmark_pos; e.env.goal = goal; e.env.symbol = symbol; e.env.tstep = tstep;
   e.env.episode = episode; e.env.N = N; e.env.T = env_episode_length; e.env.mode = 1; e.env.seed = env_seed;
-  e.counter = counter; e.T = T; e.centralized = centralized; e.deterministic = deterministic;
   const dim3 grid((unsigned)((N + COMM_EP_G - 1) / COMM_EP_G));
-  const size_t lds_bytes = sizeof(float) * COMM_EP_LDS_FLOATS;
-  const bool relu = speaker->actor_desc.use_relu != 0;
-  int rc;
-  if (speaker->actor_desc.layer_N == 0) rc = relu ? comm_episode_launch<true, 0>(grid, lds_bytes, as_stream(stream), e) : comm_episode_launch<false, 0>(grid, lds_bytes, as_stream(stream), e);
-  else rc = relu ? comm_episode_launch<true, 1>(grid, lds_bytes, as_stream(stream), e) : comm_episode_launch<false, 1>(grid, lds_bytes, as_stream(stream), e);
-  if (rc) return rc;
-  MAPPO_CHECK_LAUNCH("rollout_episode_comm");
+  constexpr int lds_bytes = sizeof(float) * COMM_EP_LDS_FLOATS;
+  if (int rc = dispatch_relu_ln<1>(ag[0].actor_desc.use_relu != 0, ag[0].actor_desc.layer_N, [&](auto R, auto L) {
+        return launch_kernel<rollout_episode_comm_kernel<R.value, L.value>, lds_bytes>(who, grid, dim3(COMM_EP_WAVES * WAVE), lds_bytes, as_stream(stream), e);
+      }))
+    return rc;
+  MAPPO_CHECK_LAUNCH(who);
   return MAPPO_OK;
 }

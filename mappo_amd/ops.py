@@ -418,15 +418,20 @@ def rollout_episode_comm(speaker, listener, T, N, env_episode_length, env_seed, 
     _lib.check(rc, "mappo_rollout_episode_comm")
 
 
+def _episode_agents(who, scenario, M, agents):
+    """The M comm_agent(...) of a separated one-launch episode as the contiguous array its entry point reads."""
+    if len(agents) != M:
+        raise ValueError(f"{who}: {scenario} is built for num_agents = {M} (got {len(agents)} agents)")
+    return (_lib.CommAgent * M)(*agents)
+
+
 def rollout_episode_adversary(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
                               deterministic, counter, centralized):
     """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_adversary env in one launch, env steps included
     (mappo_rollout_episode_adversary).  agents: the three comm_agent(...) of agents 0 (adversary), 1, 2 (good); the six env state
     tensors (SimpleAdversaryVecEnv) are read, stepped T times on the sampled indices and stored back."""
-    if len(agents) != 3:
-        raise ValueError(f"rollout_episode_adversary: simple_adversary is built for num_agents = 3 (got {len(agents)} agents)")
     f64 = torch.float64
-    arr = (_lib.CommAgent * 3)(*agents)
+    arr = _episode_agents("rollout_episode_adversary", "simple_adversary", 3, agents)
     rc = _lib.load().mappo_rollout_episode_adversary(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
                                                      _ptr(goal, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T),
                                                      int(N), int(env_episode_length), int(env_seed) & (2 ** 64 - 1),
@@ -440,10 +445,8 @@ def rollout_episode_tag(agents, T, N, env_episode_length, env_seed, agent_pos, a
     """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_tag env in one launch, env steps included
     (mappo_rollout_episode_tag).  agents: the four comm_agent(...) of agents 0 .. 2 (adversaries) and 3 (good); the five env state
     tensors (SimpleTagVecEnv) are read, stepped T times on the sampled indices and stored back."""
-    if len(agents) != 4:
-        raise ValueError(f"rollout_episode_tag: simple_tag is built for num_agents = 4 (got {len(agents)} agents)")
     f64 = torch.float64
-    arr = (_lib.CommAgent * 4)(*agents)
+    arr = _episode_agents("rollout_episode_tag", "simple_tag", 4, agents)
     rc = _lib.load().mappo_rollout_episode_tag(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
                                                _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T), int(N), int(env_episode_length),
                                                int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)), int(counter) & (2 ** 64 - 1),

@@ -71,14 +71,8 @@ class MPERunner(Runner):
             # t + *_counter_dev, every agent from its own word
             for p in self.policy:
                 p.actor._counter_dev.add_(self.episode_length)
-        if self._comm_episode_ready():
-            self._collect_episode_comm(deterministic)
-            return infos
-        if self._adversary_episode_ready():
-            self._collect_episode_adversary(deterministic)
-            return infos
-        if self._tag_episode_ready():
-            self._collect_episode_tag(deterministic)
+        if self._episode_ready():
+            self._collect_episode(deterministic)
             return infos
         for step in range(self.episode_length):
             values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env = self.collect(step, deterministic)
@@ -146,20 +140,21 @@ class MPERunner(Runner):
             b.share_obs[0].copy_(share if self.use_centralized_V else obs[agent_id])
             b.obs[0].copy_(obs[agent_id])
 
-    # ---- one rollout episode in one launch (mappo_rollout_episode_comm) ----
-    def _comm_episode_ready(self):
-        """The env is the GPU-resident simple_speaker_listener (it steps inside the launch), both policies are what the kernel is
-        built for (feed-forward, narrow, layer_N <= 1, one layer_N and activation in all four networks, the scenario's shapes) and
-        the buffers have the device layout it writes.  Anything else takes the stepwise path."""
+    # ---- one rollout episode in one launch (env.episode_launch: mappo_rollout_episode_comm / _adversary / _tag) ----
+    def _episode_ready(self):
+        """The env is GPU-resident and steps inside the launch (it has episode_launch, and its env variable episode_flag is not "0"),
+        the policies are what its kernel is built for (feed-forward, narrow, layer_N <= 1, one layer_N and activation in all
+        networks, the env's own widths) and the buffers have the device layout the launch writes.  Anything else takes the stepwise
+        path."""
         env = self.envs
-        if os.environ.get("MAPPO_COMM_EPISODE", "1") == "0" or not hasattr(env, "episode_state_comm") or self.num_agents != 2:
+        if not hasattr(env, "episode_launch") or os.environ.get(env.episode_flag, "1") == "0" or self.num_agents != env.M:
             return False
-        return self._episode_shapes_ready(env, env.listener_pos.device)
+        return self._episode_shapes_ready(env, env.episode.device)
+
+    _comm_episode_ready = _adversary_episode_ready = _tag_episode_ready = _episode_ready     # the names the per-scenario GPU tests call
 
     def _episode_shapes_ready(self, env, dev):
-        """What the one-launch episodes of the ragged envs share: feed-forward narrow policies, layer_N <= 1, one layer_N and
-        activation in all networks, the env's own widths, buffers in the device layout the launch writes.  dev: where the env's
-        tensors landed."""
+        """dev: where the env's tensors landed."""
         if not self._fused_ff():
             return False
         d0 = self.policy[0].actor.desc
@@ -176,38 +171,8 @@ class MPERunner(Runner):
         return True
 
     @torch.no_grad()
-    def _collect_episode_comm(self, deterministic=False):
+    def _collect_episode(self, deterministic=False):
         """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent."""
-        st = self.envs.episode_state_comm()
-        N = self.n_rollout_threads
-        if self._next_values is None:
-            self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
-        from mappo_amd import ops
-        ags = []
-        for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer)):
-            ags.append(ops.comm_agent(p.actor.flat, p.actor.desc, p.critic.flat, p.critic.desc, p.actor._seed, p.actor._counter_dev, b.obs, b.share_obs, b.rewards,
-                                      b.masks, b.actions, b.action_log_probs, b.value_preds, self._next_values[agent_id]))
-        ops.rollout_episode_comm(ags[0], ags[1], self.episode_length, N, st["T"], st["seed"], st["listener_pos"], st["listener_vel"],
-                                 st["landmark_pos"], st["goal"], st["symbol"], st["tstep"], st["episode"], deterministic, 0,
-                                 self.use_centralized_V)
-        for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
-            b.step = 0
-            tr.prep_rollout()
-            b.compute_returns(self._next_values[agent_id], tr.value_normalizer)
-
-    # ---- the same on simple_adversary (mappo_rollout_episode_adversary) ----
-    def _adversary_episode_ready(self):
-        """The env is the GPU-resident simple_adversary and the three policies are what the kernel is built for; anything else
-        takes the stepwise path."""
-        env = self.envs
-        if os.environ.get("MAPPO_ADV_EPISODE", "1") == "0" or not hasattr(env, "episode_state_adversary") or self.num_agents != 3:
-            return False
-        return self._episode_shapes_ready(env, env.agent_pos.device)
-
-    @torch.no_grad()
-    def _collect_episode_adversary(self, deterministic=False):
-        """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent."""
-        st = self.envs.episode_state_adversary()
         N = self.n_rollout_threads
         if self._next_values is None:
             self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
@@ -215,35 +180,7 @@ class MPERunner(Runner):
         ags = [ops.comm_agent(p.actor.flat, p.actor.desc, p.critic.flat, p.critic.desc, p.actor._seed, p.actor._counter_dev, b.obs, b.share_obs,
                               b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds, self._next_values[agent_id])
                for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer))]
-        ops.rollout_episode_adversary(ags, self.episode_length, N, st["T"], st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"],
-                                      st["goal"], st["tstep"], st["episode"], deterministic, 0, self.use_centralized_V)
-        for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
-            b.step = 0
-            tr.prep_rollout()
-            b.compute_returns(self._next_values[agent_id], tr.value_normalizer)
-
-    # ---- the same on simple_tag (mappo_rollout_episode_tag) ----
-    def _tag_episode_ready(self):
-        """The env is the GPU-resident simple_tag and the four policies are what the kernel is built for; anything else takes the
-        stepwise path."""
-        env = self.envs
-        if os.environ.get("MAPPO_TAG_EPISODE", "1") == "0" or not hasattr(env, "episode_state_tag") or self.num_agents != 4:
-            return False
-        return self._episode_shapes_ready(env, env.agent_pos.device)
-
-    @torch.no_grad()
-    def _collect_episode_tag(self, deterministic=False):
-        """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent."""
-        st = self.envs.episode_state_tag()
-        N = self.n_rollout_threads
-        if self._next_values is None:
-            self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
-        from mappo_amd import ops
-        ags = [ops.comm_agent(p.actor.flat, p.actor.desc, p.critic.flat, p.critic.desc, p.actor._seed, p.actor._counter_dev, b.obs, b.share_obs,
-                              b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds, self._next_values[agent_id])
-               for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer))]
-        ops.rollout_episode_tag(ags, self.episode_length, N, st["T"], st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"],
-                                st["tstep"], st["episode"], deterministic, 0, self.use_centralized_V)
+        self.envs.episode_launch(ags, self.episode_length, deterministic, 0, self.use_centralized_V)
         for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
             b.step = 0
             tr.prep_rollout()
