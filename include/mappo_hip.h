@@ -682,6 +682,51 @@ int mappo_rollout_episode_tag(const mappo_comm_agent *agents /*host, [4]*/, doub
                               int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                               int32_t centralized, mappo_stream_t stream);
 
+/* GPU-vectorised MPE simple_push, "keep-away" (csrc/mpe_push_env.hip, device functions in csrc/mpe_push_core.h): N environments of
+ * the fixed shape num_agents = 2, num_landmarks = 2 — agent 0 the ADVERSARY (own velocity 2, the 2 landmarks relative to itself 4,
+ * the other agent relative to itself 2 = 8 features; it is not told which landmark is the goal), agent 1 the GOOD agent (own
+ * velocity 2, the goal relative to itself 2, its own colour 3, the 2 landmarks relative to itself 4, the landmarks' colours 6, the
+ * other agent relative to itself 2 = 19 features); both move, Discrete(5); nobody speaks; the two agents (size 0.05) collide with
+ * each other, the landmarks with nothing — one launch per step.  Replaces MultiAgentEnv.step / _set_action (environment.py:117-256:
+ * u = (a1 - a2, a3 - a4) * 5, accel is None), World.step (core.py:207-322: the soft-collision force between the two agents,
+ * dist_min 0.1, damping 0.25, dt 0.1, mass 1, no speed clamp), Scenario.reset_world / reward / observation
+ * (scenarios/simple_push.py:42-107) + the vec-env's reset-on-done (env_wrappers.py:146-152).  Colours are the reference's float64
+ * sums cast to fp32: landmark k is 0.1 everywhere with [k + 1] += 0.8, the good agent 0.25 everywhere with [goal + 1] += 0.5.  State
+ * is caller-owned device memory: agent_pos / agent_vel [N][2][2] and landmark_pos [N][2][2] in float64, goal [N] int32 (the
+ * landmark index of both agents' goal_a), tstep [N] int32, episode [N] int64 (reset counter = Philox counter).  Outputs:
+ * obs_adversary [N][8], obs_good [N][19] fp32; rewards [N][2] fp32, ONE PER AGENT and never summed (world.collaborative is not set,
+ * environment.py:49-50,142): the adversary |p_good - p_goal| - |p_goal - p_adv|, the good agent -|p_good - p_goal|; dones [N][2]
+ * bool bytes.  action_mode 0: the reference's one-hots / probabilities, actions [N][2][5]; 1: indices as fp32, actions [N][2],
+ * clamped to 0..4 (1/2/3/4 = +x/-x/+y/-y).  Physics in float64 with contraction off; the contact force goes through the device's
+ * exp / log1p, so obs and rewards are held to 1e-6 of the fp32 cast of the reference's float64 values rather than to the bit.  An
+ * environment whose episode ends (tstep >= episode_length) is reset inside the same launch and returns the reset observation.
+ * Reset draws: Philox stream (seed, episode), 64-bit uniform number 16 n + k of environment n — k = 2 a, 2 a + 1: position of
+ * agent a in U(-1,1); k = 4 + 2 l, 5 + 2 l: position of landmark l in 0.8 U(-1,1); k = 8: goal = min(1, floor(2 u)), u in [0,1);
+ * k = 9..15 unused; velocities start at zero.  Both validate on the host and name the fault: num_agents == 2 (the only shape
+ * built), N >= 1, non-null pointers, action_mode 0 or 1, episode_length >= 1. */
+int mappo_mpe_push_reset(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *goal, int32_t *tstep,
+                         int64_t *episode, float *obs_adversary, float *obs_good, int32_t N, int32_t num_agents, uint64_t seed,
+                         mappo_stream_t stream);
+int mappo_mpe_push_step(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *goal, int32_t *tstep,
+                        int64_t *episode, const float *actions, int32_t action_mode, float *obs_adversary, float *obs_good,
+                        float *rewards, uint8_t *dones, int32_t N, int32_t num_agents, int32_t episode_length, uint64_t seed,
+                        mappo_stream_t stream);
+/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner (csrc/rollout_push.h): what
+ * T x (one mappo_rollout_step per agent + mappo_mpe_push_step with action_mode 1 + the agents' inserts) + one bootstrap
+ * mappo_rollout_step per agent do, bit for bit.  agents: two mappo_comm_agent (the adversary, then the good agent).  Per step
+ * t < T: agent m's actor on its observation rows of step t (step 0: obs_buf slot 0), row n sampled with (agent's seed, counter + t
+ * (+ the agent's *counter_dev), Philox index n) -> actions / logp slot t; the environments step in float64 on the sampled indices
+ * (reset-on-done after env_episode_length steps); each agent's observation -> its obs_buf slot t + 1, its share row (centralized:
+ * the two observations side by side, 8 | 19 = 27; else its own observation) -> share_buf slot t + 1, its OWN reward -> rew_buf
+ * slot t, 1 - done -> mask_buf slot t + 1.  Each critic on its share rows of step t <= T -> values, step T -> next_values.  The six
+ * state arrays are stored back at the end, so the environment continues in either path.  Host checks, each named in the error:
+ * non-null descriptors; not recurrent; layer_N <= 1; actors in 8 / 19 and out 5; critics out 1 and in 27 (centralized) or the
+ * agent's own in_dim; the same layer_N and activation in all four networks; T, N, env_episode_length >= 1; non-null pointers. */
+int mappo_rollout_episode_push(const mappo_comm_agent *agents /*host, [2]*/, double *agent_pos, double *agent_vel,
+                               double *landmark_pos, int32_t *goal, int32_t *tstep, int64_t *episode, int32_t T, int32_t N,
+                               int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
+                               int32_t centralized, mappo_stream_t stream);
+
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only
  * produces data of the SMAC shapes with agents that die and episodes that end.  obs [N][M][D], share_obs [N][M][S] ~ N(0,1);

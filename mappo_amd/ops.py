@@ -454,6 +454,20 @@ def rollout_episode_tag(agents, T, N, env_episode_length, env_seed, agent_pos, a
     _lib.check(rc, "mappo_rollout_episode_tag")
 
 
+def rollout_episode_push(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
+                         deterministic, counter, centralized):
+    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_push env in one launch, env steps included
+    (mappo_rollout_episode_push).  agents: the two comm_agent(...) of agents 0 (adversary) and 1 (good); the six env state tensors
+    (SimplePushVecEnv) are read, stepped T times on the sampled indices and stored back."""
+    f64 = torch.float64
+    arr = _episode_agents("rollout_episode_push", "simple_push", 2, agents)
+    rc = _lib.load().mappo_rollout_episode_push(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
+                                                _ptr(goal, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T),
+                                                int(N), int(env_episode_length), int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)),
+                                                int(counter) & (2 ** 64 - 1), int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode_push")
+
+
 def mlp_backward_slabs(B):
     return int(_lib.load().mappo_mlp_backward_slabs(int(B)))
 
@@ -863,6 +877,33 @@ def mpe_tag_step(agent_pos, agent_vel, landmark_pos, tstep, episode, actions, ac
                                         _ptr(obs_adv2), _ptr(obs_good), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(num_agents),
                                         int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
     _lib.check(rc, "mappo_mpe_tag_step")
+
+
+# ---- GPU-vectorised MPE simple_push (csrc/mpe_push_env.hip): one adversary + one good agent that collide, Discrete(5) each, per-agent rewards ------
+def _push_agents(who, num_agents):
+    if int(num_agents) != 2:
+        raise ValueError(f"{who}: simple_push is built for num_agents = 2: 1 adversary, 1 good agent, 2 landmarks (got {num_agents})")
+
+
+def mpe_push_reset(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, obs_adversary, obs_good, N, seed, num_agents=2):
+    _push_agents("mpe_push_reset", num_agents)
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_push_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                          _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs_adversary), _ptr(obs_good), int(N),
+                                          int(num_agents), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_push_reset")
+
+
+def mpe_push_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, actions, action_mode, obs_adversary, obs_good, rewards, dones, N,
+                  episode_length, seed, num_agents=2):
+    """action_mode 0: one-hots [N, 2, 5] | 1: fp32 indices [N, 2].  rewards [N, 2]: one per agent."""
+    _push_agents("mpe_push_step", num_agents)
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_push_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
+                                         _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(actions), int(action_mode),
+                                         _ptr(obs_adversary), _ptr(obs_good), _ptr(rewards), _ptr(dones, torch.uint8), int(N),
+                                         int(num_agents), int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_push_step")
 
 
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):

@@ -14,7 +14,8 @@ buffer contents and env state, bit for bit; MAPPO_COMM_EPISODE=0 keeps the stepw
 simple_adversary env (three agents, observations of 8 / 10 / 10 features, per-agent rewards) runs the same two ways:
 mappo_rollout_episode_adversary, MAPPO_ADV_EPISODE=0 for the stepwise path.  The GPU-resident simple_tag env (four agents,
 observations of 16 / 16 / 16 / 14 features, per-agent rewards) likewise: mappo_rollout_episode_tag, MAPPO_TAG_EPISODE=0 for the
-stepwise path."""
+stepwise path; and the GPU-resident simple_push env (two agents that collide, observations of 8 / 19 features, per-agent rewards):
+mappo_rollout_episode_push, MAPPO_PUSH_EPISODE=0.  None of them is named below: the env brings `episode_launch` and `episode_flag`."""
 import os
 import time
 
