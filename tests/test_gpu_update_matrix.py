@@ -256,7 +256,7 @@ def _reference(a, actor, critic, rows, obs, sobs, avail, actions, old_logp, adv,
     ad, cd = copy.deepcopy(actor).double(), copy.deepcopy(critic).double()
     t = lambda x: torch.from_numpy(x[rows]).double()
     act = t(active).view(-1, 1)
-    lp, ent, _ = ad.evaluate_actions(t(obs), None, t(actions).view(-1, 1), None, t(avail), act)
+    lp, ent, _ = ad.evaluate_actions(t(obs), None, t(actions).view(-1, 1), None, None if avail is None else t(avail), act)
     vals = cd(t(sobs), None, None)[0]
     ret_t = t(ret).view(-1, 1)
     tgt = vn.normalize(ret_t.float()).double() if a.use_valuenorm else ret_t
