@@ -472,8 +472,11 @@ int mappo_reduce_clip_adam(const float *slabs, int32_t n_slabs, int64_t slab_str
  * State is caller-owned device memory: agent_pos / agent_vel [N][M][2] and landmark_pos [N][L][2] in float64 (the reference's
  * NumPy dtype), tstep [N] int32, episode [N] int64 (reset counter = Philox counter).  Outputs: obs [N][M][4+2L+4(M-1)] fp32,
  * rewards [N][M] fp32 (shared reward), dones [N][M] bool bytes.  action_mode 0: actions = the reference's actions_env
- * [N][M][5] (one-hot); 1: action indices [N][M] as fp32 (the buffer's own format).  An environment whose episode ends is
- * reset inside the same launch and returns the reset observation, as DummyVecEnv / SubprocVecEnv do. */
+ * [N][M][5] (one-hot, or any row of five weights such as probabilities: the force is 5 * [a1 - a2, a3 - a4] of what is given,
+ * environment.py:223-235); 1: action indices [N][M] as fp32 (the buffer's own format).  An index is truncated towards zero to an
+ * int and moves the agent only if that int is 1..4: 2.7 acts as 2, and every other value (-3, 9, 0) as 0, no force.  There is no
+ * clamp to the nearest move (simple_tag's kernel clamps; this one does not); the sampler only produces 0..4.  An environment whose
+ * episode ends is reset inside the same launch and returns the reset observation, as DummyVecEnv / SubprocVecEnv do. */
 int mappo_mpe_spread_reset(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *tstep, int64_t *episode, float *obs,
                            int32_t N, int32_t M, int32_t L, uint64_t seed, mappo_stream_t stream);
 int mappo_mpe_spread_step(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *tstep, int64_t *episode,

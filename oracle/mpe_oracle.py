@@ -1,12 +1,14 @@
 """CPU restatement (NumPy float64) of MPE `simple_spread` as the reference steps it — TEST INFRASTRUCTURE: only tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this file.
 
-PARITY UNPINNED.  The reference's own modules cannot be imported in the build container without stand-ins
-(`onpolicy/envs/mpe/core.py:2` imports seaborn, `onpolicy/envs/mpe/environment.py:1` imports gym; neither is installed), and
-the reference holds no test or fixture for this path.  The functions below restate the cited lines; the GPU kernel
-(mappo_amd/csrc/mpe_env.hip) is checked against them and against properties of the dynamics (action / reaction of the
+PARITY PINNED to episodes stepped by the reference's own environment (imported behind small stand-ins for gym and seaborn by the
+generators under tests/golden/): 3 agents x 3 landmarks in tests/golden/mpe_envs.npz (tests/test_mpe_reference.py) and seven other
+shapes from 1 x 1 to 8 x 8, with crowded starts, scripted contact distances and probability actions, in
+tests/golden/mpe_spread_shapes.npz (tests/test_mpe_spread_shapes.py) — observations, rewards, dones and the float64 state of every
+step within 1e-12 (measured: 7e-15; the margin is for another libm's logaddexp).  The functions below restate the cited lines; the
+GPU kernel (mappo_amd/csrc/mpe_env.hip) is checked against them and against properties of the dynamics (action / reaction of the
 collision force, damping of the total momentum, agent-permutation equivariance, translation invariance of the relative
-observations) in tests/test_mpe_env.py.
+observations) in tests/test_mpe_env.py, and against the fixtures themselves in tests/test_gpu_mpe_spread_shapes.py.
 
     world.step            onpolicy/envs/mpe/core.py:207-229   (action force, environment force, integrate)
     collision force       onpolicy/envs/mpe/core.py:283-322   (softmax penetration, contact_force 1e2, contact_margin 1e-3)

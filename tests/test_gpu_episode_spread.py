@@ -64,14 +64,14 @@ CASES = [  # (M, L, centralized, N, layer_N, relu, feature norm, env episode len
 ]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("M,L,centralized,N,layer_N,relu,fnorm,env_T", CASES)
-def test_episode_spread_launch_matches_stepwise(gpu_device, M, L, centralized, N, layer_N, relu, fnorm, env_T):
+def _both_paths(M, L, centralized, N, layer_N, relu, fnorm, env_T, T=25):
     """Two eager episodes through each path: every buffer array, the bootstrap values, the counter word and the env's five state
-    tensors agree bit for bit."""
+    tensors agree bit for bit.  Returns the states [path][episode] (path 1: the one-launch episode) and the env state both paths
+    started from."""
     runs = []
     for episode in (False, True):
-        r, env = _runner(episode, centralized, layer_N, relu, fnorm, N, M, L, env_T=env_T)
+        r, env = _runner(episode, centralized, layer_N, relu, fnorm, N, M, L, T=T, env_T=env_T)
+        start = {n: getattr(env, n).cpu().numpy().copy() for n in ENV_NAMES}
         states = []
         for _ in range(2):
             r.rollout()
@@ -82,11 +82,80 @@ def test_episode_spread_launch_matches_stepwise(gpu_device, M, L, centralized, N
         _assert_same(runs[0][e], runs[1][e], what=f"episode {e}: ")
     assert not torch.equal(runs[1][0]["actions"], runs[1][1]["actions"])          # fresh sampling stream
     assert not torch.equal(runs[1][0]["obs"], runs[1][1]["obs"])
+    return runs, start
+
+
+def _replay_through_oracle(buf, start, env_T, reset_states):
+    """The actions `buf` recorded, replayed through the NumPy oracle from the env state `start` (saved before the launch), give its
+    observations, rewards and masks (1e-6: the fp32 cast of the outputs, the tolerance of
+    test_mpe_env.py::test_kernel_matches_oracle_step_by_step).  reset_states(n): the state environment n takes when its episode
+    ends.  Returns the number of episodes that ended."""
+    from oracle import mpe_oracle as R
+    obs, rew, masks = (buf[k].cpu().numpy() for k in ("obs", "rewards", "masks"))
+    T, N, M = rew.shape[:3]
+    assert len(set(start["tstep"].tolist())) == 1
+    ref = R.SimpleSpreadRef(start["agent_pos"], start["agent_vel"], start["landmark_pos"], env_T, tstep=int(start["tstep"][0]))
+    np.testing.assert_allclose(obs[0], ref.obs(), rtol=1e-6, atol=1e-6)
+    acts = buf["actions"].cpu().numpy().astype(np.int64).reshape(T, N, M)
+    assert acts.min() >= 0 and acts.max() <= 4 and len(np.unique(acts)) > 1
+    ended = 0
+    for t in range(T):
+        o_ref, r_ref, d_ref = ref.step(np.eye(5)[acts[t]], reset_states)
+        ended += int(d_ref[:, 0].sum())
+        np.testing.assert_allclose(obs[t + 1], o_ref, rtol=1e-6, atol=1e-6, err_msg=f"obs, step {t}")
+        np.testing.assert_allclose(rew[t], r_ref, rtol=1e-6, atol=1e-6, err_msg=f"rewards, step {t}")
+        np.testing.assert_array_equal(masks[t + 1, :, :, 0], 1.0 - d_ref, err_msg=f"masks, step {t}")
+    return ended
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,L,centralized,N,layer_N,relu,fnorm,env_T", CASES)
+def test_episode_spread_launch_matches_stepwise(gpu_device, M, L, centralized, N, layer_N, relu, fnorm, env_T):
+    runs, _ = _both_paths(M, L, centralized, N, layer_N, relu, fnorm, env_T)
     if env_T == 10:
         assert float(runs[1][0]["masks"][1:25].min()) == 0.0                       # a reset inside the launch
         assert int(runs[1][0]["env.tstep"].max()) == 5 and int(runs[1][1]["env.tstep"].max()) == 0      # 25 = 2 x 10 + 5; 50 = 5 x 10
     else:
         assert float(runs[1][0]["masks"][1:25].min()) == 1.0 and float(runs[1][0]["masks"][25].max()) == 0.0
+
+
+SHAPE_CASES = [  # (M, L, centralized, N, layer_N, relu, feature norm, env episode length, T): shapes the 3 x 3 fixture does not reach
+    (1, 1, True, 17, 1, True, True, 25, 6),       # S = 6; 16 environments per tile: one full tile and one single row
+    (2, 5, True, 9, 0, False, False, 25, 6),      # S = 36, M < L
+    (5, 2, False, 4, 1, False, True, 25, 6),      # G = 3: 4 environments leave a partial tile
+    (7, 1, False, 3, 0, True, False, 25, 6),      # G = 2: 14 of 16 rows
+    (8, 8, False, 3, 1, True, True, 25, 6),       # D = 48, G = 2: a full 16-row tile and a half one
+    (6, 2, False, 5, 1, False, False, 3, 5),      # resets inside the launch; the second launch starts at tstep 2
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,L,centralized,N,layer_N,relu,fnorm,env_T,T", SHAPE_CASES)
+def test_episode_spread_other_shapes(gpu_device, M, L, centralized, N, layer_N, relu, fnorm, env_T, T):
+    """What test_episode_spread_launch_matches_stepwise asserts (bit identity of the two paths) and what
+    test_episode_spread_matches_oracle asserts (the recorded actions replayed through the oracle), at other M, L and tile fills.  The
+    replay shares no code with mpe_step_env; an episode that ends takes the host Philox's reset draw, not the kernel's."""
+    import mpe_spread_np as MS
+    runs, start = _both_paths(M, L, centralized, N, layer_N, relu, fnorm, env_T, T=T)
+    first, second = runs[1]
+    D = 4 + 2 * L + 4 * (M - 1)
+    assert tuple(first["obs"].shape) == (T + 1, N, M, D) and tuple(first["share_obs"].shape) == (T + 1, N, M, M * D if centralized else D)
+    episode = start["episode"].copy()
+    assert episode.tolist() == [1] * N and start["tstep"].tolist() == [0] * N                 # warmup's reset
+
+    def reset_states(n):                                     # stream (seed 1, the environment's next episode number)
+        episode[n] += 1
+        pos, lpos = MS.reset_draws(1, int(episode[n]), n + 1, M, L)
+        return pos[n], np.zeros((M, 2)), lpos[n]
+    ended = _replay_through_oracle(first, start, env_T, reset_states)
+    assert ended == N * (T // env_T)
+    np.testing.assert_array_equal(first["env.episode"].cpu().numpy(), episode)
+    assert first["env.tstep"].cpu().tolist() == [T % env_T] * N and second["env.tstep"].cpu().tolist() == [2 * T % env_T] * N
+    if centralized:                                          # the environment's M observation rows side by side, once per agent
+        side = first["obs"].reshape(T + 1, N, 1, M * D).expand(T + 1, N, M, M * D)
+        assert torch.equal(first["share_obs"], side)
+    else:
+        assert torch.equal(first["share_obs"][1:], first["obs"][1:])
 
 
 def _counting(names):
@@ -171,10 +240,9 @@ def test_episode_spread_matches_oracle(gpu_device, deterministic):
     """Independent of the stepwise kernels: the actions the fused episode recorded, replayed through the NumPy oracle from the state
     saved before the launch, give the buffer's observations and rewards (1e-6: the fp32 cast of the outputs, the tolerance of
     test_mpe_env.py::test_kernel_matches_oracle_step_by_step).  deterministic=True covers the argmax path."""
-    from oracle import mpe_oracle as R
     T, N, M = 25, 64, 3
     r, env = _runner(True, N=N)
-    pos, vel, lpos = (getattr(env, n).cpu().numpy().copy() for n in ENV_NAMES[:3])
+    start = {n: getattr(env, n).cpu().numpy().copy() for n in ENV_NAMES}
     b = r.buffer
     if deterministic:
         nv = torch.empty(N * M, device=b.device)
@@ -182,19 +250,10 @@ def test_episode_spread_matches_oracle(gpu_device, deterministic):
     else:
         r.rollout()
     torch.cuda.synchronize()
-    ref = R.SimpleSpreadRef(pos, vel, lpos, T)
-    np.testing.assert_allclose(b.obs[0].cpu().numpy(), ref.obs(), rtol=1e-6, atol=1e-6)
-    acts = b.actions.cpu().numpy().astype(np.int64).reshape(T, N, M)
-    assert acts.min() >= 0 and acts.max() <= 4 and len(np.unique(acts)) > 1
-    obs, rew, masks = b.obs.cpu().numpy(), b.rewards.cpu().numpy(), b.masks.cpu().numpy()
 
     def reset_states(n):                                     # the oracle adopts the kernel's own reset draw (the last step's)
         return env.agent_pos[n].cpu().numpy(), env.agent_vel[n].cpu().numpy(), env.landmark_pos[n].cpu().numpy()
-    for t in range(T):
-        o_ref, r_ref, d_ref = ref.step(np.eye(5)[acts[t]], reset_states)
-        np.testing.assert_allclose(obs[t + 1], o_ref, rtol=1e-6, atol=1e-6, err_msg=f"obs, step {t}")
-        np.testing.assert_allclose(rew[t], r_ref, rtol=1e-6, atol=1e-6, err_msg=f"rewards, step {t}")
-        np.testing.assert_array_equal(masks[t + 1, :, :, 0], 1.0 - d_ref, err_msg=f"masks, step {t}")
+    assert _replay_through_oracle({k: getattr(b, k) for k in BUF_NAMES}, start, T, reset_states) == N
     assert int(env.tstep.max()) == 0 and int(env.episode.min()) == 2          # warmup's reset + the time-limit reset of step T - 1
 
 

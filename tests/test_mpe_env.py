@@ -1,6 +1,6 @@
-"""MPE simple_spread.  PARITY UNPINNED: the reference's env modules need seaborn / gym, which are not
-installed, and it holds no fixtures for them (see oracle/mpe_oracle.py).  CPU tests pin the oracle's restatement with
-properties the dynamics must have; the GPU tests compare the HIP kernel with the oracle step by step (float64 physics on
+"""MPE simple_spread.  The oracle (oracle/mpe_oracle.py) is pinned to episodes stepped by the reference's own
+environment: 3 x 3 in tests/test_mpe_reference.py, seven other shapes in tests/test_mpe_spread_shapes.py (1e-12).  The CPU tests
+here add properties the dynamics must have; the GPU tests compare the HIP kernel with the oracle step by step (float64 physics on
 both sides; tolerance 1e-6 = the fp32 cast of the outputs) and run a full training iteration on the device env."""
 import numpy as np
 import pytest
