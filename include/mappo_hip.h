@@ -730,6 +730,50 @@ int mappo_rollout_episode_push(const mappo_comm_agent *agents /*host, [2]*/, dou
                                int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                                int32_t centralized, mappo_stream_t stream);
 
+/* GPU-vectorised MPE simple_crypto (csrc/mpe_crypto_env.hip, device functions in csrc/mpe_crypto_core.h): N environments of
+ * num_agents = 3 and num_landmarks L = 2, 3 or 4 — agent 0 the ADVERSARY "Eve" (observes what the speaker said: 4 features), agent 1
+ * the good listener "Bob" (the key, then what the speaker said: 8), agent 2 the SPEAKER "Alice" (the goal, then the key: 8).  Nobody
+ * moves and nothing collides; every agent only speaks, Discrete(4) = dim_c, and landmark k's colour is the one-hot e_k of R^4 — one
+ * launch per step.  Replaces MultiAgentEnv.step / _set_action (environment.py:117-256: an agent that does not move speaks its whole
+ * action vector), World.step (core.py:280-287: state.c = action.c, no noise), Scenario.reset_world / reward / observation
+ * (scenarios/simple_crypto.py:47-171) + the vec-env's reset-on-done (env_wrappers.py:146-152).  State is caller-owned device
+ * memory, all integers: goal [N] and key [N] int32 (landmark indices 0 .. L - 1), comm [N][3] int32 (the symbol each agent last
+ * said, -1: nothing said, the reference's zero vector), tstep [N] int32, episode [N] int64 (reset counter = Philox counter); the
+ * positions the reference also draws enter no observation and no reward and are not kept.  Outputs: obs_eve [N][4] = Alice's c,
+ * obs_bob [N][8] = e_key | Alice's c, obs_alice [N][8] = e_goal | e_key, fp32; rewards [N][3] fp32, ONE PER AGENT and never summed
+ * (world.collaborative is not set, environment.py:49-50,142): with d(a) = |c_a - e_goal|^2 (0 or 2 for a one-hot; an agent whose c
+ * is all zeros is skipped, as in the reference) Eve gets -d(Eve), Bob and Alice d(Eve) - d(Bob); dones [N][3] bool bytes.
+ * action_mode 0: the reference's one-hots / probabilities, actions [N][3][4], the symbol is the index of the row's first maximum;
+ * 1: indices as fp32, actions [N][3], clamped to 0..3.  Every value is a small integer, so obs and rewards EQUAL the fp32 cast of
+ * the reference's.  An environment whose episode ends (tstep >= episode_length) is reset inside the same launch and returns the
+ * reset observation (nothing said yet: Eve sees zeros, Bob e_key | 0).  Reset draws: Philox stream (seed, episode), 32-bit word
+ * 2 n + k of environment n — k = 0: goal = (word * L) >> 32 in 64-bit arithmetic; k = 1: key, the same map of its own word.  Both
+ * validate on the host and name the fault: num_agents == 3, num_landmarks 2..4, N >= 1, non-null pointers, action_mode 0 or 1,
+ * episode_length >= 1. */
+int mappo_mpe_crypto_reset(int32_t *goal, int32_t *key, int32_t *comm, int32_t *tstep, int64_t *episode, float *obs_eve,
+                           float *obs_bob, float *obs_alice, int32_t N, int32_t num_agents, int32_t num_landmarks, uint64_t seed,
+                           mappo_stream_t stream);
+int mappo_mpe_crypto_step(int32_t *goal, int32_t *key, int32_t *comm, int32_t *tstep, int64_t *episode, const float *actions,
+                          int32_t action_mode, float *obs_eve, float *obs_bob, float *obs_alice, float *rewards, uint8_t *dones,
+                          int32_t N, int32_t num_agents, int32_t num_landmarks, int32_t episode_length, uint64_t seed,
+                          mappo_stream_t stream);
+/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner (csrc/rollout_crypto.h):
+ * what T x (one mappo_rollout_step per agent + mappo_mpe_crypto_step with action_mode 1 + the agents' inserts) + one bootstrap
+ * mappo_rollout_step per agent do, bit for bit.  agents: three mappo_comm_agent (Eve, Bob, Alice).  Per step t < T: agent m's actor
+ * on its observation rows of step t (step 0: obs_buf slot 0), row n sampled with (agent's seed, counter + t (+ the agent's
+ * *counter_dev), Philox index n) -> actions / logp slot t; the environments step on the sampled symbols (reset-on-done after
+ * env_episode_length steps); each agent's observation -> its obs_buf slot t + 1, its share row (centralized: the three
+ * observations side by side, 4 | 8 | 8 = 20; else its own observation) -> share_buf slot t + 1, its OWN reward -> rew_buf slot t,
+ * 1 - done -> mask_buf slot t + 1.  Each critic on its share rows of step t <= T -> values, step T -> next_values.  The five state
+ * arrays are stored back at the end, so the environment continues in either path.  Host checks, each named in the error: non-null
+ * descriptors; num_landmarks 2..4; not recurrent; layer_N <= 1; actors in 4 / 8 / 8 and out 4; critics out 1 and in 20
+ * (centralized) or the agent's own in_dim; the same layer_N and activation in all six networks; T, N, env_episode_length >= 1;
+ * non-null pointers. */
+int mappo_rollout_episode_crypto(const mappo_comm_agent *agents /*host, [3]*/, int32_t *goal, int32_t *key, int32_t *comm,
+                                 int32_t *tstep, int64_t *episode, int32_t T, int32_t N, int32_t num_landmarks,
+                                 int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
+                                 int32_t centralized, mappo_stream_t stream);
+
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only
  * produces data of the SMAC shapes with agents that die and episodes that end.  obs [N][M][D], share_obs [N][M][S] ~ N(0,1);

@@ -468,6 +468,21 @@ def rollout_episode_push(agents, T, N, env_episode_length, env_seed, agent_pos, 
     _lib.check(rc, "mappo_rollout_episode_push")
 
 
+def rollout_episode_crypto(agents, T, N, env_episode_length, env_seed, goal, key, comm, tstep, episode, deterministic, counter,
+                           centralized, num_landmarks=2):
+    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_crypto env in one launch, env steps included
+    (mappo_rollout_episode_crypto).  agents: the three comm_agent(...) of agents 0 (Eve), 1 (Bob) and 2 (Alice); the five env state
+    tensors (SimpleCryptoVecEnv) are read, stepped T times on the sampled symbols and stored back."""
+    i32 = torch.int32
+    arr = _episode_agents("rollout_episode_crypto", "simple_crypto", 3, agents)
+    _crypto_shape("rollout_episode_crypto", 3, num_landmarks)
+    rc = _lib.load().mappo_rollout_episode_crypto(arr, _ptr(goal, i32), _ptr(key, i32), _ptr(comm, i32), _ptr(tstep, i32),
+                                                  _ptr(episode, torch.int64), int(T), int(N), int(num_landmarks), int(env_episode_length),
+                                                  int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)), int(counter) & (2 ** 64 - 1),
+                                                  int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode_crypto")
+
+
 def mlp_backward_slabs(B):
     return int(_lib.load().mappo_mlp_backward_slabs(int(B)))
 
@@ -904,6 +919,36 @@ def mpe_push_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, acti
                                          _ptr(obs_adversary), _ptr(obs_good), _ptr(rewards), _ptr(dones, torch.uint8), int(N),
                                          int(num_agents), int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
     _lib.check(rc, "mappo_mpe_push_step")
+
+
+# ---- GPU-vectorised MPE simple_crypto (csrc/mpe_crypto_env.hip): Eve, Bob and Alice only speak, Discrete(4) each, per-agent rewards ------
+def _crypto_shape(who, num_agents, num_landmarks):
+    if int(num_agents) != 3:
+        raise ValueError(f"{who}: simple_crypto is built for num_agents = 3: adversary Eve, listener Bob, speaker Alice (got {num_agents})")
+    if not 2 <= int(num_landmarks) <= 4:
+        raise ValueError(f"{who}: simple_crypto takes num_landmarks = 2, 3 or 4, a landmark's colour being a one-hot of dim_c = 4 "
+                         f"(got {num_landmarks})")
+
+
+def mpe_crypto_reset(goal, key, comm, tstep, episode, obs_eve, obs_bob, obs_alice, N, seed, num_agents=3, num_landmarks=2):
+    _crypto_shape("mpe_crypto_reset", num_agents, num_landmarks)
+    i32 = torch.int32
+    rc = _lib.load().mappo_mpe_crypto_reset(_ptr(goal, i32), _ptr(key, i32), _ptr(comm, i32), _ptr(tstep, i32), _ptr(episode, torch.int64),
+                                            _ptr(obs_eve), _ptr(obs_bob), _ptr(obs_alice), int(N), int(num_agents), int(num_landmarks),
+                                            int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_crypto_reset")
+
+
+def mpe_crypto_step(goal, key, comm, tstep, episode, actions, action_mode, obs_eve, obs_bob, obs_alice, rewards, dones, N, episode_length,
+                    seed, num_agents=3, num_landmarks=2):
+    """action_mode 0: one-hots [N, 3, 4] | 1: fp32 indices [N, 3].  rewards [N, 3]: one per agent."""
+    _crypto_shape("mpe_crypto_step", num_agents, num_landmarks)
+    i32 = torch.int32
+    rc = _lib.load().mappo_mpe_crypto_step(_ptr(goal, i32), _ptr(key, i32), _ptr(comm, i32), _ptr(tstep, i32), _ptr(episode, torch.int64),
+                                           _ptr(actions), int(action_mode), _ptr(obs_eve), _ptr(obs_bob), _ptr(obs_alice), _ptr(rewards),
+                                           _ptr(dones, torch.uint8), int(N), int(num_agents), int(num_landmarks), int(episode_length),
+                                           int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_crypto_step")
 
 
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):

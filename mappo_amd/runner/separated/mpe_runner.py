@@ -15,7 +15,8 @@ simple_adversary env (three agents, observations of 8 / 10 / 10 features, per-ag
 mappo_rollout_episode_adversary, MAPPO_ADV_EPISODE=0 for the stepwise path.  The GPU-resident simple_tag env (four agents,
 observations of 16 / 16 / 16 / 14 features, per-agent rewards) likewise: mappo_rollout_episode_tag, MAPPO_TAG_EPISODE=0 for the
 stepwise path; and the GPU-resident simple_push env (two agents that collide, observations of 8 / 19 features, per-agent rewards):
-mappo_rollout_episode_push, MAPPO_PUSH_EPISODE=0.  None of them is named below: the env brings `episode_launch` and `episode_flag`."""
+mappo_rollout_episode_push, MAPPO_PUSH_EPISODE=0; and the GPU-resident simple_crypto env (three agents that only speak, observations of
+4 / 8 / 8 features, per-agent rewards): mappo_rollout_episode_crypto, MAPPO_CRYPTO_EPISODE=0.  None of them is named below: the env brings `episode_launch` and `episode_flag`."""
 import os
 import time
 
@@ -141,7 +142,7 @@ class MPERunner(Runner):
             b.share_obs[0].copy_(share if self.use_centralized_V else obs[agent_id])
             b.obs[0].copy_(obs[agent_id])
 
-    # ---- one rollout episode in one launch (env.episode_launch: mappo_rollout_episode_comm / _adversary / _tag) ----
+    # ---- one rollout episode in one launch (env.episode_launch: mappo_rollout_episode_comm / _adversary / _tag / _push / _crypto) ----
     def _episode_ready(self):
         """The env is GPU-resident and steps inside the launch (it has episode_launch, and its env variable episode_flag is not "0"),
         the policies are what its kernel is built for (feed-forward, narrow, layer_N <= 1, one layer_N and activation in all

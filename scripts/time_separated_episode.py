@@ -1,14 +1,15 @@
 """Time the rollout of one episode of the SEPARATED runner on a GPU-resident MPE env with agents of different shapes, T = 25, two ways:
-`python scripts/time_separated_episode.py OUT.json --scenario {comm,adversary,tag,push} [--n 128] [--rollouts 20]`.
+`python scripts/time_separated_episode.py OUT.json --scenario {comm,adversary,tag,push,crypto} [--n 128] [--rollouts 20]`.
 
     comm       SimpleSpeakerListenerVecEnv (speaker 3 -> 3, listener 11 -> 5)
     adversary  SimpleAdversaryVecEnv (adversary 8 -> 5, two good agents 10 -> 5, per-agent rewards)
     tag        SimpleTagVecEnv (three adversaries 16 -> 5, one good agent 14 -> 5, per-agent rewards)
     push       SimplePushVecEnv (adversary 8 -> 5, good agent 19 -> 5, the two collide, per-agent rewards)
+    crypto     SimpleCryptoVecEnv (Eve 4 -> 4, Bob and Alice 8 -> 4, nobody moves, per-agent rewards)
 
     stepwise   T x (one mappo_rollout_step per agent + the env's step launch + the agents' inserts) + one bootstrap launch per agent,
                launched from Python (the env's episode_flag, e.g. MAPPO_TAG_EPISODE, = 0)
-    episode    the env's episode_launch (mappo_rollout_episode_comm / _adversary / _tag / _push), one launch from Python (the flag = 1)
+    episode    the env's episode_launch (mappo_rollout_episode_comm / _adversary / _tag / _push / _crypto), one launch from Python (the flag = 1)
 
 Each is MPERunner.rollout() as training calls it, so the per-agent GAE launches that follow the episode are inside every number.
 Three untimed rollouts first, then REPEATS repeats of ROLLOUTS back-to-back rollouts, each repeat between two device
@@ -26,9 +27,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 REPEATS = 7
-# env class, and the agents whose reward is never positive (a check that the episode ran the scenario's own rewards)
+# env class, and the agents whose reward is always negative (a check that the episode ran the scenario's own rewards; none in
+# simple_crypto, where Eve's reward is -2 or 0)
 SCENARIOS = dict(comm=("SimpleSpeakerListenerVecEnv", (0, 1)), adversary=("SimpleAdversaryVecEnv", (0,)), tag=("SimpleTagVecEnv", ()),
-                 push=("SimplePushVecEnv", (1,)))
+                 push=("SimplePushVecEnv", (1,)), crypto=("SimpleCryptoVecEnv", ()))
 
 
 def runner(env_cls, N, T):
