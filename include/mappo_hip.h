@@ -774,6 +774,45 @@ int mappo_rollout_episode_crypto(const mappo_comm_agent *agents /*host, [3]*/, i
                                  int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                                  int32_t centralized, mappo_stream_t stream);
 
+/* GPU-vectorised MPE simple_world_comm (csrc/mpe_world_comm_env.hip, device functions in csrc/mpe_world_comm_core.h): N environments
+ * of the fixed shape num_adversaries = 4, num_good_agents = 2, num_landmarks = 1 (num_agents = 6) — agents 0..3 the ADVERSARIES
+ * (size 0.075, accel 3, max_speed 1), agent 0 their LEADER, agents 4, 5 the GOOD agents (size 0.045, accel 4, max_speed 1.3); five
+ * landmarks in world order [landmark 0.2, food0, food1 0.03, forest0, forest1 0.3], none moves and only landmark 0 collides.  Every
+ * agent moves, Discrete(5); the leader also says one of dim_c = 4 words, MultiDiscrete([[0, 4], [0, 3]]) — one launch per step.
+ * Observation of agent m: own velocity 2, own position 2, the 5 landmarks relative to it 10, the five other agents relative to it
+ * in world-agent order 10, then for an adversary the two good agents' velocities 4, its own in_forest flags 2 (+1 inside forest f,
+ * else -1) and the leader's word of THIS step 4 (34 features); for a good agent its in_forest flags 2 and the other good agent's
+ * velocity 2 (28).  Another agent's position, and a good one's velocity, is written as 0 unless it is visible to m: both inside the
+ * same forest, or both inside no forest, or m is the leader.  Replaces MultiAgentEnv.step / _set_action (environment.py:117-256: the
+ * MultiDiscrete split at :198-205, u = (a1 - a2, a3 - a4) * accel, the leader's c = its second head), World.step (core.py:207-322:
+ * action force accel * u — accel a second time —, the soft-collision force between every pair of colliding entities of which one
+ * can move, pairs a < b over the agents then landmark 0; damping 0.25; the max_speed clamp; dt 0.1; mass 1; state.c = action.c),
+ * Scenario.reset_world / reward / observation (scenarios/simple_world_comm.py:100-112,141-199,225-288) + the vec-env's reset-on-done
+ * (env_wrappers.py:146-152).  State is caller-owned device memory: agent_pos / agent_vel [N][6][2] and landmark_pos [N][5][2] in
+ * float64, tstep [N] int32, episode [N] int64 (reset counter = Philox counter); the leader's word is not state, the step writes it
+ * into the observations it returns.  obs: a HOST array of six device pointers, [N][34] x 4 then [N][28] x 2, fp32.  rewards [N][6]
+ * fp32, ONE PER AGENT and never summed (world.collaborative is not set, environment.py:49-50,142): an adversary -0.1 x its distance
+ * to the nearest good agent + 5 x (pairs of a good agent and ANY adversary within 0.12); a good agent -5 per adversary within 0.12,
+ * -2 x the boundary penalty of |x| and of |y| (0 below 0.9, 10 (x - 0.9) below 1, else min(exp(2 x - 2), 10)), +2 per food item
+ * within 0.075, +0.05 x its distance to the nearest food item; dones [N][6] bool bytes.  actions: a HOST array of device pointers —
+ * action_mode 0: the reference's one-hots / probabilities, actions[0] [N][9] (the leader's move and word side by side) and
+ * actions[1..5] [N][5]; 1: actions[0] = indices as fp32 [N][7] in the column order leader move, leader word, agents 1..5, clamped to
+ * 0..4 (1/2/3/4 = +x/-x/+y/-y) and 0..3, actions[1..5] not read.  Physics in float64 with contraction off; the contact force and
+ * the penalty go through the device's exp / log1p, so float obs and rewards match the fp32 cast of the reference's float64 values to
+ * 1e-6 rather than to the bit; flags, hidden zeros, the word and dones are equal.  An environment whose episode ends (tstep >=
+ * episode_length) is reset inside the same launch and returns the reset observation, the word in it zero; reset writes a zero word
+ * too.  Reset draws: Philox stream (seed, episode), 64-bit uniform number 32 n + k of environment n — k = 2 a, 2 a + 1: position of
+ * agent a in U(-1,1); k = 12 + 2 l, 13 + 2 l: position of landmark l in 0.8 U(-1,1); k = 22..31 unused; velocities start at zero.
+ * Both validate on the host and name the fault: num_agents == 6 and num_landmarks == 1 (the only shape built), N >= 1, non-null
+ * pointers (the arrays' entries included), action_mode 0 or 1, episode_length >= 1. */
+int mappo_mpe_world_comm_reset(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *tstep, int64_t *episode,
+                               float *const *obs /*host, [6]*/, int32_t N, int32_t num_agents, int32_t num_landmarks, uint64_t seed,
+                               mappo_stream_t stream);
+int mappo_mpe_world_comm_step(double *agent_pos, double *agent_vel, double *landmark_pos, int32_t *tstep, int64_t *episode,
+                              const float *const *actions /*host, [6]*/, int32_t action_mode, float *const *obs /*host, [6]*/,
+                              float *rewards, uint8_t *dones, int32_t N, int32_t num_agents, int32_t num_landmarks,
+                              int32_t episode_length, uint64_t seed, mappo_stream_t stream);
+
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only
  * produces data of the SMAC shapes with agents that die and episodes that end.  obs [N][M][D], share_obs [N][M][S] ~ N(0,1);

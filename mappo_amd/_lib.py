@@ -146,6 +146,8 @@ SIGNATURES = {
     "mappo_mpe_crypto_reset": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _P]),
     "mappo_mpe_crypto_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _U64, _P]),
     "mappo_rollout_episode_crypto": (C.c_int, [C.POINTER(CommAgent), _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _U64, _I32, _U64, _I32, _P]),
+    "mappo_mpe_world_comm_reset": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _P]),
+    "mappo_mpe_world_comm_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _U64, _P]),
     "mappo_profile_arm": (C.c_int, [_I32, _P, _P]),
     "mappo_selftest_mfma": (C.c_int, [_P, _P, _P, _P]),
 }

@@ -125,7 +125,8 @@ def mpe_defaults(parser):
                         help="MPE scenario; GPU-resident envs exist for simple_spread, simple_reference, simple_speaker_listener "
                              "(num_agents 2, share_policy False), simple_adversary (num_agents 3, share_policy False), simple_tag (num_agents 4: 3 "
                              "adversaries and 1 good agent, share_policy False), simple_push (num_agents 2, num_landmarks 2, "
-                             "share_policy False) and simple_crypto (num_agents 3, num_landmarks 2 to 4, share_policy False): "
+                             "share_policy False), simple_crypto (num_agents 3, num_landmarks 2 to 4, share_policy False) and "
+                             "simple_world_comm (num_agents 6: 4 adversaries, 2 good agents, num_landmarks 1, share_policy False, mappo): "
                              "mappo_amd.envs")
     parser.add_argument("--num_landmarks", type=int, default=3)
     parser.add_argument("--num_agents", type=int, default=2)

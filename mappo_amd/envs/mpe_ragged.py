@@ -1,8 +1,10 @@
 """What the GPU-resident MPE envs with agents of DIFFERENT shapes share (mpe_speaker_listener, mpe_adversary, mpe_tag, mpe_push,
-mpe_crypto): the vec-env
+mpe_crypto, mpe_world_comm): the vec-env
 flags the runners read, the per-agent spaces, the two recycled output sets, and the forms of `actions` that `step` accepts.  A
 scenario's class sets `M`, `obs_dims`, `act_dims` and `episode_flag`, owns its state tensors and calls its own kernels in `reset`,
-`step` and `episode_launch` — the separated runner's one-launch episode, which the env variable `episode_flag` = "0" switches off."""
+`step` and `episode_launch` — the separated runner's one-launch episode, which the env variable `episode_flag` = "0" switches off.
+An env with a MultiDiscrete agent (mpe_world_comm) replaces `action_space` and brings its own `_parse_actions`; it has no
+`episode_launch`."""
 import torch
 
 from ..utils.util import Discrete

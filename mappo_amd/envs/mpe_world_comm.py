@@ -1,0 +1,98 @@
+"""GPU-vectorised MPE `simple_world_comm` behind the reference's vec-env contract for agents of DIFFERENT shapes, DIFFERENT rewards and
+DIFFERENT action spaces:
+
+    reset() -> [obs_adv0 .. obs_adv3 [N, 34], obs_good0, obs_good1 [N, 28]]
+    step(actions) -> ([the six observations], rewards [N, 6, 1], dones [N, 6] bool, infos)
+
+(`onpolicy/envs/env_wrappers.py`, `onpolicy/envs/mpe/environment.py:117-256`, `scenarios/simple_world_comm.py`).  The reference's
+`train_mpe.py` starts it with `--scenario_name simple_world_comm --num_adversaries 4 --num_good_agents 2 --num_landmarks 1`: agents
+0..3, the slower adversaries, chase agents 4 and 5, the faster and smaller good agents, who collect two food items and may hide in two
+forests.  An agent sees another one only if both are in the same forest or both are in none — except agent 0, the adversaries'
+LEADER, who sees everybody and says one of four words that every adversary hears in the same step.  So `action_space[0]` is
+`MultiDiscrete([[0, 4], [0, 3]])` (move, word) and the other five are `Discrete(5)`; the separated runner takes such an env because it
+declares `accepts_multidiscrete_agents`.  The world is not collaborative, so `rewards[:, m]` is agent m's OWN reward.  The two
+observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_world_comm_env.hip) and
+everything stays in HBM.  There is no one-launch episode for this env ("Out of scope"): the runner steps it.  What the envs
+of this kind share is in mpe_ragged.py.
+
+`step` takes
+  * the reference's one-hots as a per-agent list: `[N, 9]` for the leader (its two heads side by side), `[N, 5]` for the others;
+  * or indices: one tensor `[N, 7]` in the column order leader move, leader word, agents 1..5 (`accepts_index_actions`), or a
+    per-agent list of `[N, 2]` for the leader and `[N]` / `[N, 1]` for the others.
+Physics run in float64 as in the reference's NumPy code, with float outputs within 1e-6 of the fp32 cast of the reference's
+(tests/golden/mpe_world_comm.npz; the contact force goes through exp and log, which are not NumPy's to the bit) and the in_forest
+flags, the zeros of hidden agents, the word and the dones equal; initial states come from a counter-based Philox stream (seed,
+episode, env), not from NumPy's global generator."""
+import torch
+
+from .. import ops
+from ..utils.util import Discrete, MultiDiscrete
+from .mpe_ragged import RaggedMPEVecEnv
+
+
+class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
+    M, L = 6, 5                                                     # L: landmark, food0, food1, forest0, forest1
+    obs_dims, act_dims = (34, 34, 34, 34, 28, 28), (9, 5, 5, 5, 5, 5)
+    accepts_multidiscrete_agents = True                             # step takes K index columns / K one-hots side by side per such agent
+
+    def __init__(self, n_rollout_threads, num_agents=6, episode_length=25, seed=1, device="cuda", num_adversaries=4, num_good_agents=2,
+                 num_landmarks=1):
+        if (int(num_agents), int(num_adversaries), int(num_good_agents), int(num_landmarks)) != (6, 4, 2, 1):
+            raise ValueError(f"simple_world_comm is built for num_agents = 6: 4 adversaries (the first their leader), 2 good agents, "
+                             f"1 landmark (got num_agents {num_agents}, num_adversaries {num_adversaries}, num_good_agents "
+                             f"{num_good_agents}, num_landmarks {num_landmarks})")
+        super().__init__(n_rollout_threads, episode_length, seed, device)
+        self.action_space = [MultiDiscrete([[0, 4], [0, 3]])] + [Discrete(5) for _ in range(self.M - 1)]      # environment.py:62-90
+        f64 = dict(dtype=torch.float64, device=self.device)
+        self.agent_pos = torch.zeros(self.N, self.M, 2, **f64)
+        self.agent_vel = torch.zeros(self.N, self.M, 2, **f64)
+        self.landmark_pos = torch.zeros(self.N, self.L, 2, **f64)
+        self.tstep = torch.zeros(self.N, dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(self.N, dtype=torch.int64, device=self.device)
+
+    def set_state(self, agent_pos, agent_vel, landmark_pos, tstep=0):
+        """Test hook: load explicit states (float64 arrays / tensors [N, 6, 2], [N, 6, 2], [N, 5, 2]).  `episode`, the reset counter
+        that keys the Philox stream, is left as it is."""
+        self.agent_pos.copy_(torch.as_tensor(agent_pos, dtype=torch.float64))
+        self.agent_vel.copy_(torch.as_tensor(agent_vel, dtype=torch.float64))
+        self.landmark_pos.copy_(torch.as_tensor(landmark_pos, dtype=torch.float64))
+        self.tstep.fill_(int(tstep))
+
+    def state_tensors(self):
+        return dict(agent_pos=self.agent_pos, agent_vel=self.agent_vel, landmark_pos=self.landmark_pos, tstep=self.tstep, episode=self.episode)
+
+    def _bad_actions(self, what):
+        return ValueError(f"{type(self).__name__}.step: {what}: expected a list of 6 per-agent tensors — one-hots [N, 9] (the leader's move "
+                          f"and word side by side) and [N, 5] x 5, or indices [N, 2] (move, word) and [N] / [N, 1] x 5 — or one index tensor "
+                          f"[N, 7] (leader move, leader word, agents 1..5), with N = {self.N}")
+
+    def _parse_actions(self, actions):
+        """-> (mode, packed).  mode 0: the list of per-agent one-hots [N, 9], [N, 5] x 5; mode 1: indices [N, 7]."""
+        N, M = self.N, self.M
+        f32 = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(a)).to(self.device, torch.float32)
+        if isinstance(actions, (list, tuple)):
+            if len(actions) != M:
+                raise self._bad_actions(f"{len(actions)} per-agent entries")
+            a = [f32(x) for x in actions]
+            if all(tuple(x.shape) == (N, n) for x, n in zip(a, self.act_dims)):
+                return 0, [x.contiguous() for x in a]
+            if tuple(a[0].shape) == (N, 2) and all(tuple(x.shape) in ((N,), (N, 1)) for x in a[1:]):
+                return 1, torch.cat([a[0]] + [x.reshape(N, 1) for x in a[1:]], dim=1)
+            raise self._bad_actions(f"per-agent actions of shapes {[tuple(x.shape) for x in a]}")
+        a = f32(actions)
+        if tuple(a.shape) == (N, M + 1):
+            return 1, a.contiguous()
+        raise self._bad_actions(f"actions of shape {tuple(a.shape)}")
+
+    def reset(self):
+        obs = self._next_out()[:self.M]
+        ops.mpe_world_comm_reset(self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep, self.episode, obs, self.N, self.seed, self.M)
+        return list(obs)
+
+    def step(self, actions):
+        mode, act = self._parse_actions(actions)
+        out = self._next_out()
+        obs, rew, dones = out[:self.M], out[self.M], out[self.M + 1]
+        ops.mpe_world_comm_step(self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep, self.episode, act, mode, obs,
+                                rew.view(self.N, self.M), dones.view(torch.uint8), self.N, self.T, self.seed, self.M)
+        return list(obs), rew, dones, None

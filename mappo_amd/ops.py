@@ -951,6 +951,51 @@ def mpe_crypto_step(goal, key, comm, tstep, episode, actions, action_mode, obs_e
     _lib.check(rc, "mappo_mpe_crypto_step")
 
 
+# ---- GPU-vectorised MPE simple_world_comm (csrc/mpe_world_comm_env.hip): four adversaries, the first a MultiDiscrete (5, 4) leader, +
+# two good agents, Discrete(5) each, per-agent rewards ------
+def _world_comm_shape(who, num_agents, num_adversaries, num_good_agents, num_landmarks):
+    if (int(num_agents), int(num_adversaries), int(num_good_agents), int(num_landmarks)) != (6, 4, 2, 1):
+        raise ValueError(f"{who}: simple_world_comm is built for num_agents = 6: 4 adversaries (the first their leader), 2 good agents, "
+                         f"1 landmark (got num_agents {num_agents}, num_adversaries {num_adversaries}, num_good_agents {num_good_agents}, "
+                         f"num_landmarks {num_landmarks})")
+
+
+def _ptr_array(tensors, n, what, allow_none=False):
+    """A host array of n device pointers (fp32 tensors; None -> NULL where allowed)."""
+    if len(tensors) != n:
+        raise ValueError(f"{what}: {len(tensors)} tensors, needs {n}")
+    ptrs = [_ptr(t, allow_none=allow_none) for t in tensors]
+    return (C.c_void_p * n)(*[None if q is None else q.value for q in ptrs])
+
+
+def mpe_world_comm_reset(agent_pos, agent_vel, landmark_pos, tstep, episode, obs, N, seed, num_agents=6, num_adversaries=4,
+                         num_good_agents=2, num_landmarks=1):
+    """obs: the six per-agent output tensors, [N, 34] x 4 then [N, 28] x 2."""
+    _world_comm_shape("mpe_world_comm_reset", num_agents, num_adversaries, num_good_agents, num_landmarks)
+    f64 = torch.float64
+    rc = _lib.load().mappo_mpe_world_comm_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
+                                                _ptr(episode, torch.int64), _ptr_array(list(obs), 6, "mpe_world_comm_reset: obs"),
+                                                int(N), int(num_agents), int(num_landmarks), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_world_comm_reset")
+
+
+def mpe_world_comm_step(agent_pos, agent_vel, landmark_pos, tstep, episode, actions, action_mode, obs, rewards, dones, N, episode_length, seed,
+                        num_agents=6, num_adversaries=4, num_good_agents=2, num_landmarks=1):
+    """action_mode 0: actions = the six one-hot tensors, [N, 9] of the leader (move | word) and [N, 5] x 5 | 1: actions = one tensor of
+    fp32 indices [N, 7]: leader move, leader word, agents 1..5.  obs as in mpe_world_comm_reset; rewards [N, 6]: one per agent."""
+    _world_comm_shape("mpe_world_comm_step", num_agents, num_adversaries, num_good_agents, num_landmarks)
+    f64 = torch.float64
+    acts = list(actions) if int(action_mode) == 0 else [actions] + [None] * 5
+    if acts[0] is None:
+        raise ValueError("tensor required")
+    rc = _lib.load().mappo_mpe_world_comm_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
+                                               _ptr(episode, torch.int64), _ptr_array(acts, 6, "mpe_world_comm_step: actions", allow_none=int(action_mode) != 0),
+                                               int(action_mode), _ptr_array(list(obs), 6, "mpe_world_comm_step: obs"),
+                                               _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(num_agents), int(num_landmarks),
+                                               int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.check(rc, "mappo_mpe_world_comm_step")
+
+
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):
     """P steps of the synthetic SMAC-shaped env in one launch: pools obs [P, N, M, D], share_obs, avail, rewards [P, N], dones [P, N, M]."""
     P, N, M, D = obs.shape

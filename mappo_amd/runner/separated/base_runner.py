@@ -23,8 +23,11 @@ class Runner(_SharedRunner):
         from mappo_amd.algorithms.r_mappo.r_mappo import R_MAPPO as TrainAlgo
         from mappo_amd.algorithms.r_mappo.algorithm.rMAPPOPolicy import R_MAPPOPolicy as Policy
         self.policy, self.trainer, self.buffer = [], [], []
+        # a MultiDiscrete agent among the others: only on an env that declares it takes such an agent's K index columns / K one-hots
+        # side by side (accepts_multidiscrete_agents, e.g. SimpleWorldCommVecEnv); its buffer then carries [T, N, K] actions
+        multi_ok = bool(getattr(self.envs, "accepts_multidiscrete_agents", False))
         for agent_id in range(self.num_agents):
-            if self.envs.action_space[agent_id].__class__.__name__ == "MultiDiscrete":
+            if self.envs.action_space[agent_id].__class__.__name__ == "MultiDiscrete" and not multi_ok:
                 raise NotImplementedError("MultiDiscrete action space under the separated runner (share_policy = False): the K-wide action "
                                           "columns are built for the shared MPERunner only")
         for agent_id in range(self.num_agents):

@@ -16,20 +16,49 @@ mappo_rollout_episode_adversary, MAPPO_ADV_EPISODE=0 for the stepwise path.  The
 observations of 16 / 16 / 16 / 14 features, per-agent rewards) likewise: mappo_rollout_episode_tag, MAPPO_TAG_EPISODE=0 for the
 stepwise path; and the GPU-resident simple_push env (two agents that collide, observations of 8 / 19 features, per-agent rewards):
 mappo_rollout_episode_push, MAPPO_PUSH_EPISODE=0; and the GPU-resident simple_crypto env (three agents that only speak, observations of
-4 / 8 / 8 features, per-agent rewards): mappo_rollout_episode_crypto, MAPPO_CRYPTO_EPISODE=0.  None of them is named below: the env brings `episode_launch` and `episode_flag`."""
+4 / 8 / 8 features, per-agent rewards): mappo_rollout_episode_crypto, MAPPO_CRYPTO_EPISODE=0.  None of them is named below: the env brings `episode_launch` and `episode_flag`.
+
+One agent may be MultiDiscrete among Discrete ones where the env declares `accepts_multidiscrete_agents` (the GPU-resident
+simple_world_comm: its leader moves and speaks): that agent's buffer carries [T, N, K] actions and log-probs, `collect` keeps all K
+columns, `pack_actions` builds what the env takes, and every agent collects through collect_into — neither mappo_rollout_step nor a
+one-launch episode covers such a run."""
 import os
 import time
 
 import numpy as np
 import torch
 
+from mappo_amd.utils.util import head_dims_of
+
 from .base_runner import Runner, _t2n, env_takes_device_actions
+
+
+def pack_actions(acts, action_spaces, index_form):
+    """The agents' sampled indices -> what `envs.step` takes, where some agent is MultiDiscrete.  acts: per-agent integer tensors (any
+    device), [N] / [N, 1] for a Discrete agent and [N, K] for a MultiDiscrete one.  index_form: ONE fp32 tensor [N, sum K_m], the
+    agents' columns side by side in agent order (simple_world_comm: leader move, leader word, agents 1..5) — for a device env with
+    accepts_index_actions.  Otherwise the reference's per-agent list (separated/mpe_runner.py:118-124): np.eye(n)[a] for Discrete(n),
+    np.eye(high_i + 1)[action[:, i]] of a MultiDiscrete agent's heads side by side."""
+    N = acts[0].shape[0]
+    cols = [a.reshape(N, -1).long() for a in acts]
+    if index_form:
+        return torch.cat(cols, dim=1).to(torch.float32)
+    out = []
+    for a, space in zip(cols, action_spaces):
+        dims = head_dims_of(space)
+        if a.shape[1] != len(dims):
+            raise ValueError(f"pack_actions: {a.shape[1]} action columns for {space}")
+        out.append(torch.cat([torch.eye(d, dtype=torch.float32, device=a.device)[a[:, j]] for j, d in enumerate(dims)], dim=1))
+    return out
 
 
 class MPERunner(Runner):
     def __init__(self, config):
         super().__init__(config)
         self._eye = None
+        # a MultiDiscrete agent among the others (base_runner._build let it through: the env declares accepts_multidiscrete_agents):
+        # K action / log-prob columns for that agent, so per-agent lists where the homogeneous path stacks
+        self._multi = any(s.__class__.__name__ == "MultiDiscrete" for s in self.envs.action_space[:self.num_agents])
         obs_dims = [self.buffer[m].obs.shape[-1] for m in range(self.num_agents)]
         act_dims = [self.envs.action_space[m].n for m in range(self.num_agents)]
         # agents of different shapes: per-agent observation lists, per-agent one-hot widths
@@ -117,7 +146,11 @@ class MPERunner(Runner):
     def _actions_env(self, envs, acts):
         """acts: per-agent index tensors [N] -> what envs.step takes.  Same shapes: np.eye(n)[action], [N, M, n], as ever.  Different
         shapes: indices [N, M] for an env that decodes them itself (accepts_index_actions), else a per-agent list of one-hots
-        [N, n_m] — NumPy arrays for a host env."""
+        [N, n_m] — NumPy arrays for a host env.  With a MultiDiscrete agent acts are [N, K_m] and pack_actions builds either form."""
+        if self._multi:
+            device = env_takes_device_actions(envs)
+            out = pack_actions(acts, envs.action_space, bool(getattr(envs, "accepts_index_actions", False)) and device)
+            return out if device else [_t2n(x) for x in out]
         if not self._ragged:
             n_act = envs.action_space[0].n
             if self._eye is None or self._eye.shape[0] != n_act:
@@ -214,12 +247,15 @@ class MPERunner(Runner):
                 act, ra, rc = tr.policy.collect_step_fused(b, step, None, self.use_centralized_V, deterministic=deterministic), None, None
             else:
                 act, ra, rc = tr.policy.collect_into(b, step, deterministic=deterministic)       # outputs land in b.{actions, action_log_probs, value_preds}[step]
-            values.append(b.value_preds[step]); actions.append(act.view(N, 1)); logps.append(b.action_log_probs[step])
+            values.append(b.value_preds[step]); actions.append(act.view(N, -1)); logps.append(b.action_log_probs[step])
             rnn_a.append(ra); rnn_c.append(rc)
-        actions = torch.stack(actions, dim=1)                       # [N, M, 1]
-        actions_env = self._actions_env(self.envs, [actions[:, agent_id, 0].long() for agent_id in range(self.num_agents)])
         stack = lambda xs: torch.stack([x.view(N, *x.shape[1:]) if x is not None else torch.zeros(N, self.recurrent_N, self.hidden_size,
                                                                                                  device=self.device) for x in xs], dim=1)
+        if self._multi:                                             # [N, K_m] per agent: all K columns of a MultiDiscrete agent, lists
+            actions_env = self._actions_env(self.envs, [a.long() for a in actions])
+            return torch.stack(values, dim=1), actions, logps, stack(rnn_a), stack(rnn_c), actions_env
+        actions = torch.stack(actions, dim=1)                       # [N, M, 1]
+        actions_env = self._actions_env(self.envs, [actions[:, agent_id, 0].long() for agent_id in range(self.num_agents)])
         return torch.stack(values, dim=1), actions, torch.stack(logps, dim=1), stack(rnn_a), stack(rnn_c), actions_env
 
     # separated/mpe_runner.py:153-178
@@ -256,7 +292,7 @@ class MPERunner(Runner):
             for agent_id in range(self.num_agents):
                 self.trainer[agent_id].prep_rollout()
                 a, rnn[agent_id] = self.trainer[agent_id].policy.act(obs[agent_id], rnn[agent_id], masks[:, agent_id], deterministic=True)
-                acts.append(a.view(N))
+                acts.append(a.view(N, -1) if self._multi else a.view(N))
             obs, rewards, dones, _ = envs.step(self._actions_env(envs, [a.long() for a in acts]))
             obs, _ = self._obs_agents(obs)
             dones = self._dev(dones, torch.bool).view(N, self.num_agents)

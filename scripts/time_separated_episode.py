@@ -1,11 +1,14 @@
 """Time the rollout of one episode of the SEPARATED runner on a GPU-resident MPE env with agents of different shapes, T = 25, two ways:
-`python scripts/time_separated_episode.py OUT.json --scenario {comm,adversary,tag,push,crypto} [--n 128] [--rollouts 20]`.
+`python scripts/time_separated_episode.py OUT.json --scenario {comm,adversary,tag,push,crypto,world_comm} [--n 128] [--rollouts 20]`.
 
     comm       SimpleSpeakerListenerVecEnv (speaker 3 -> 3, listener 11 -> 5)
     adversary  SimpleAdversaryVecEnv (adversary 8 -> 5, two good agents 10 -> 5, per-agent rewards)
     tag        SimpleTagVecEnv (three adversaries 16 -> 5, one good agent 14 -> 5, per-agent rewards)
     push       SimplePushVecEnv (adversary 8 -> 5, good agent 19 -> 5, the two collide, per-agent rewards)
     crypto     SimpleCryptoVecEnv (Eve 4 -> 4, Bob and Alice 8 -> 4, nobody moves, per-agent rewards)
+    world_comm SimpleWorldCommVecEnv (leader 34 -> MultiDiscrete (5, 4), three adversaries 34 -> 5, two good agents 28 -> 5, 192-wide
+               centralized critics, per-agent rewards): stepwise only, through collect_into — the env has no episode_launch, and this
+               is the baseline a one-launch episode for it will be judged against
 
     stepwise   T x (one mappo_rollout_step per agent + the env's step launch + the agents' inserts) + one bootstrap launch per agent,
                launched from Python (the env's episode_flag, e.g. MAPPO_TAG_EPISODE, = 0)
@@ -28,9 +31,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 REPEATS = 7
 # env class, and the agents whose reward is always negative (a check that the episode ran the scenario's own rewards; none in
-# simple_crypto, where Eve's reward is -2 or 0)
+# simple_crypto, where Eve's reward is -2 or 0, and none in simple_world_comm, where a contact pays the adversaries 5)
 SCENARIOS = dict(comm=("SimpleSpeakerListenerVecEnv", (0, 1)), adversary=("SimpleAdversaryVecEnv", (0,)), tag=("SimpleTagVecEnv", ()),
-                 push=("SimplePushVecEnv", (1,)), crypto=("SimpleCryptoVecEnv", ()))
+                 push=("SimplePushVecEnv", (1,)), crypto=("SimpleCryptoVecEnv", ()), world_comm=("SimpleWorldCommVecEnv", ()))
 
 
 def runner(env_cls, N, T):
@@ -53,8 +56,10 @@ def main(out, scenario, N, rollouts):
     T = 25
     env_cls, negative = getattr(envs, SCENARIOS[scenario][0]), SCENARIOS[scenario][1]
     res = []
-    for name, flag in (("stepwise", "0"), ("episode", "1")):
-        os.environ[env_cls.episode_flag] = flag
+    one_launch = hasattr(env_cls, "episode_launch")
+    for name, flag in (("stepwise", "0"), ("episode", "1")) if one_launch else (("stepwise", "0"),):
+        if one_launch:
+            os.environ[env_cls.episode_flag] = flag
         r = runner(env_cls, N, T)
         assert r._episode_ready() == (flag == "1")
         for _ in range(3):
