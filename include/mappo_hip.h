@@ -812,6 +812,27 @@ int mappo_mpe_world_comm_step(double *agent_pos, double *agent_vel, double *land
                               const float *const *actions /*host, [6]*/, int32_t action_mode, float *const *obs /*host, [6]*/,
                               float *rewards, uint8_t *dones, int32_t N, int32_t num_agents, int32_t num_landmarks,
                               int32_t episode_length, uint64_t seed, mappo_stream_t stream);
+/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner
+ * (csrc/rollout_world_comm.h): what T x (mappo_rollout_step_md with the heads (5, 4) for the leader + one mappo_rollout_step per
+ * other agent + mappo_mpe_world_comm_step with action_mode 1 + the agents' inserts) write into everything but the values, bit for
+ * bit.  agents: six mappo_comm_agent (the leader, adversaries 1, 2, 3, then the two good agents).  Per step t < T: agent m's actor
+ * on its observation rows of step t (step 0: obs_buf slot 0), row n sampled with (agent's seed, counter + t (+ the agent's
+ * *counter_dev), Philox index n; the leader's head k: (k << 32) | n) -> actions / logp slot t, [T][N] and for the leader [T][N][2]
+ * (move, word); the environments step in float64 on the sampled indices (reset-on-done after env_episode_length steps); each
+ * agent's observation -> its obs_buf slot t + 1 (the word of step t in the adversaries' last four features, zeros where the
+ * environment reset), its share row (centralized: the six observations side by side, 34 x 4 | 28 x 2 = 192; else its own
+ * observation) -> share_buf slot t + 1, its OWN reward -> rew_buf slot t, 1 - done -> mask_buf slot t + 1.  The CRITICS DO NOT RUN
+ * in this launch: values and next_values are neither read nor written; the caller runs each critic once afterwards on the agent's
+ * share_buf viewed as [(T + 1) N][S] (slot T is the bootstrap value).  The critic descriptors are checked all the same, so that
+ * what is refused here is what the sibling launches refuse.  The five state arrays are stored back at the end, so the environment
+ * continues in either path.  Host checks, each named in the error: non-null descriptors; not recurrent; layer_N <= 1; actors in
+ * 34 / out 9 (leader), in 34 / out 5 (x 3), in 28 / out 5 (x 2); critics out 1 and in 192 (centralized) or the agent's own in_dim;
+ * the same layer_N and activation in all twelve networks; T, N, env_episode_length >= 1; non-null pointers.  A refused call
+ * returns MAPPO_EINVAL and launches nothing. */
+int mappo_rollout_episode_world_comm(const mappo_comm_agent *agents /*host, [6]*/, double *agent_pos, double *agent_vel,
+                                     double *landmark_pos, int32_t *tstep, int64_t *episode, int32_t T, int32_t N,
+                                     int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
+                                     int32_t centralized, mappo_stream_t stream);
 
 /* ---- benchmark utility: the synthetic SMAC-shaped vec-env of bench.py / scripts (mappo_amd/envs/synthetic.py), one launch per
  * step.  Not a reference interface (the reference's envs are CPU processes, onpolicy/envs/starcraft2/StarCraft2_Env.py): it only

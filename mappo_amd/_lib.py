@@ -140,6 +140,7 @@ SIGNATURES = {
     "mappo_mpe_tag_reset": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _U64, _P]),
     "mappo_mpe_tag_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _P]),
     "mappo_rollout_episode_tag": (C.c_int, [C.POINTER(CommAgent), _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _I32, _U64, _I32, _P]),
+    "mappo_rollout_episode_world_comm": (C.c_int, [C.POINTER(CommAgent), _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _I32, _U64, _I32, _P]),
     "mappo_mpe_push_reset": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _U64, _P]),
     "mappo_mpe_push_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _P]),
     "mappo_rollout_episode_push": (C.c_int, [C.POINTER(CommAgent), _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _U64, _I32, _U64, _I32, _P]),

@@ -38,6 +38,8 @@
 #define MPE_WC_DRAWS 32
 
 __host__ __device__ constexpr int mpe_wc_obs_dim(int m) { return m < MPE_WC_ADV ? MPE_WC_OBS_A : MPE_WC_OBS_G; }
+// where agent m's observation starts in the centralized share row (the six observations side by side)
+__host__ __device__ constexpr int mpe_wc_obs_off(int m) { return m < MPE_WC_ADV ? m * MPE_WC_OBS_A : MPE_WC_ADV * MPE_WC_OBS_A + (m - MPE_WC_ADV) * MPE_WC_OBS_G; }
 // per-agent physics (simple_world_comm.py:25-28) and the landmarks' sizes (:35,42,49)
 __host__ __device__ constexpr double mpe_wc_size(int m) { return m < MPE_WC_ADV ? 0.075 : 0.045; }
 __host__ __device__ constexpr double mpe_wc_accel(int m) { return m < MPE_WC_ADV ? 3.0 : 4.0; }
@@ -72,6 +74,22 @@ struct MpeWcAction {
   float c[MPE_WC_C];
 };
 
+// mode 1, one index as fp32 -> what it decodes to (shared with the one-launch episode, rollout_world_comm.h, which reads the indices
+// from its LDS action tile): a move index, clamped to 0 .. 4, is u = (a1 - a2, a3 - a4) of its one-hot; a word index, clamped to
+// 0 .. 3, is its one-hot
+__device__ __forceinline__ void mpe_wc_move_idx(float idx, double (&u)[2]) {
+  int k = (int)idx;
+  k = k < 0 ? 0 : (k > 4 ? 4 : k);
+  u[0] = k == 1 ? 1.0 : (k == 2 ? -1.0 : 0.0);
+  u[1] = k == 3 ? 1.0 : (k == 4 ? -1.0 : 0.0);
+}
+__device__ __forceinline__ void mpe_wc_word_idx(float idx, float (&c)[MPE_WC_C]) {
+  int w = (int)idx;
+  w = w < 0 ? 0 : (w > MPE_WC_C - 1 ? MPE_WC_C - 1 : w);
+#pragma unroll
+  for (int j = 0; j < MPE_WC_C; ++j) c[j] = j == w ? 1.f : 0.f;
+}
+
 // environment.py:194-256 for environment n.  The MultiDiscrete split (:198-205) cuts the leader's [9] into move [0, 5) and word
 // [5, 9); indices out of range go to the nearest.
 __device__ __forceinline__ void mpe_wc_decode(const MpeWcArgs &a, int n, MpeWcAction &d) {
@@ -81,20 +99,14 @@ __device__ __forceinline__ void mpe_wc_decode(const MpeWcArgs &a, int n, MpeWcAc
       const float *am = a.act[m] + (size_t)n * (m == 0 ? MPE_WC_ACT_LEADER : MPE_WC_U);
       d.u[m][0] = (double)am[1] - (double)am[2]; d.u[m][1] = (double)am[3] - (double)am[4];
     } else {
-      int k = (int)a.act[0][(size_t)n * MPE_WC_ACT_IDX + (m == 0 ? 0 : m + 1)];
-      k = k < 0 ? 0 : (k > 4 ? 4 : k);
-      d.u[m][0] = k == 1 ? 1.0 : (k == 2 ? -1.0 : 0.0);             // the one-hot of index k through the line above
-      d.u[m][1] = k == 3 ? 1.0 : (k == 4 ? -1.0 : 0.0);
+      mpe_wc_move_idx(a.act[0][(size_t)n * MPE_WC_ACT_IDX + (m == 0 ? 0 : m + 1)], d.u[m]);
     }
   }
   if (a.mode == 0) {
 #pragma unroll
     for (int j = 0; j < MPE_WC_C; ++j) d.c[j] = a.act[0][(size_t)n * MPE_WC_ACT_LEADER + MPE_WC_U + j];
   } else {
-    int w = (int)a.act[0][(size_t)n * MPE_WC_ACT_IDX + 1];
-    w = w < 0 ? 0 : (w > MPE_WC_C - 1 ? MPE_WC_C - 1 : w);
-#pragma unroll
-    for (int j = 0; j < MPE_WC_C; ++j) d.c[j] = j == w ? 1.f : 0.f;
+    mpe_wc_word_idx(a.act[0][(size_t)n * MPE_WC_ACT_IDX + 1], d.c);
   }
 }
 

@@ -1,5 +1,5 @@
 // rollout_separated.h — what the one-launch episodes of the SEPARATED runner share (rollout_comm.h, rollout_adversary.h,
-// rollout_tag.h, rollout_push.h, rollout_crypto.h): M agents of different shapes, each with its own actor, critic and SeparatedReplayBuffer, on a
+// rollout_tag.h, rollout_push.h, rollout_crypto.h; rollout_world_comm.h uses the checks and the actors' half of the fill): M agents of different shapes, each with its own actor, critic and SeparatedReplayBuffer, on a
 // GPU-resident env whose steps run inside the launch.  The kernels differ — where the weights live and which wave steps the
 // environments; their headers say why — but around them they are one thing:
 //   the argument block (SepEpisodeArgs: two CommNet per agent, the env's own args, the agents' buffer arrays);

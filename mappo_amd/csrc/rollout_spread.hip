@@ -1,7 +1,7 @@
 // rollout_spread.hip — the one-launch rollout episodes on the GPU-resident environments: simple_spread (see rollout_spread.h) and
 // simple_reference (see rollout_reference.h) and, for the separated runner, simple_speaker_listener (see rollout_comm.h), simple_adversary (see
 // rollout_adversary.h), simple_tag (see rollout_tag.h), simple_push (see rollout_push.h) and simple_crypto (see
-// rollout_crypto.h)
+// rollout_crypto.h) and simple_world_comm (see rollout_world_comm.h: the actors and the environments, the critics run afterwards)
 #include "mlp_host.h"
 #include "rollout_spread.h"
 #include "rollout_reference.h"
@@ -10,3 +10,4 @@
 #include "rollout_tag.h"
 #include "rollout_push.h"
 #include "rollout_crypto.h"
+#include "rollout_world_comm.h"

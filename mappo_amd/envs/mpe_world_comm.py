@@ -12,8 +12,10 @@ LEADER, who sees everybody and says one of four words that every adversary hears
 `MultiDiscrete([[0, 4], [0, 3]])` (move, word) and the other five are `Discrete(5)`; the separated runner takes such an env because it
 declares `accepts_multidiscrete_agents`.  The world is not collaborative, so `rewards[:, m]` is agent m's OWN reward.  The two
 observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_world_comm_env.hip) and
-everything stays in HBM.  There is no one-launch episode for this env ("Out of scope"): the runner steps it.  What the envs
-of this kind share is in mpe_ragged.py.
+everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`, an attribute the env has only then,
+mappo_rollout_episode_world_comm: the six actors and the env steps; the critics run once afterwards, `episode_critics_after`).  That
+path is opt-in, MAPPO_WORLD_COMM_EPISODE=1 (`episode_default` is "0"): it samples with the one-launch step's arithmetic, which is not
+the stepwise collect's to the bit.  What the envs of this kind share is in mpe_ragged.py.
 
 `step` takes
   * the reference's one-hots as a per-agent list: `[N, 9]` for the leader (its two heads side by side), `[N, 5]` for the others;
@@ -23,6 +25,8 @@ Physics run in float64 as in the reference's NumPy code, with float outputs with
 (tests/golden/mpe_world_comm.npz; the contact force goes through exp and log, which are not NumPy's to the bit) and the in_forest
 flags, the zeros of hidden agents, the word and the dones equal; initial states come from a counter-based Philox stream (seed,
 episode, env), not from NumPy's global generator."""
+import os
+
 import torch
 
 from .. import ops
@@ -34,6 +38,9 @@ class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
     M, L = 6, 5                                                     # L: landmark, food0, food1, forest0, forest1
     obs_dims, act_dims = (34, 34, 34, 34, 28, 28), (9, 5, 5, 5, 5, 5)
     accepts_multidiscrete_agents = True                             # step takes K index columns / K one-hots side by side per such agent
+    episode_flag = "MAPPO_WORLD_COMM_EPISODE"                       # "1": the separated runner's one-launch episode; unset / "0": stepwise
+    episode_default = "0"                                           # opt-in: the stepwise collect does not sample with the launch's bits
+    episode_critics_after = True                                    # the launch runs actors + env; the runner runs the critics after it
 
     def __init__(self, n_rollout_threads, num_agents=6, episode_length=25, seed=1, device="cuda", num_adversaries=4, num_good_agents=2,
                  num_landmarks=1):
@@ -60,6 +67,22 @@ class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
 
     def state_tensors(self):
         return dict(agent_pos=self.agent_pos, agent_vel=self.agent_vel, landmark_pos=self.landmark_pos, tstep=self.tstep, episode=self.episode)
+
+    @property
+    def episode_launch(self):
+        """The capability behind the separated runner's one-launch episode.  It is opt-in, so an env of a run that did not ask for it
+        (MAPPO_WORLD_COMM_EPISODE unset or "0") does not have the attribute at all: whoever asks `hasattr(env, "episode_launch")`
+        — the runner, and everything written before this path existed — sees the stepwise env it always saw.
+        Caveats: the answer follows os.environ at the time of the access, not of construction; the runner gates on
+        episode_default by itself, so this does no work of its own there; and it is the instance that lacks the attribute — the
+        class always shows the property (scripts/time_separated_episode.py asks the class)."""
+        if os.environ.get(self.episode_flag, self.episode_default) == "0":
+            raise AttributeError("episode_launch: the one-launch episode of simple_world_comm is opt-in (MAPPO_WORLD_COMM_EPISODE=1)")
+        return self._episode_launch
+
+    def _episode_launch(self, agents, T, deterministic, counter, centralized):
+        ops.rollout_episode_world_comm(agents, T, self.N, self.T, self.seed, self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep,
+                                       self.episode, deterministic, counter, centralized)
 
     def _bad_actions(self, what):
         return ValueError(f"{type(self).__name__}.step: {what}: expected a list of 6 per-agent tensors — one-hots [N, 9] (the leader's move "

@@ -454,6 +454,22 @@ def rollout_episode_tag(agents, T, N, env_episode_length, env_seed, agent_pos, a
     _lib.check(rc, "mappo_rollout_episode_tag")
 
 
+def rollout_episode_world_comm(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, tstep, episode, deterministic,
+                               counter, centralized):
+    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_world_comm env in one launch, env steps included
+    (mappo_rollout_episode_world_comm) — the six ACTORS only: values / next_values are not written, the caller runs each critic
+    afterwards on share_obs.  agents: the six comm_agent(...) of agent 0 (the leader, whose actions / logp are [T, N, 2]), 1 .. 3
+    (adversaries) and 4, 5 (good); the five env state tensors (SimpleWorldCommVecEnv) are read, stepped T times on the sampled
+    indices and stored back."""
+    f64 = torch.float64
+    arr = _episode_agents("rollout_episode_world_comm", "simple_world_comm", 6, agents)
+    rc = _lib.load().mappo_rollout_episode_world_comm(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
+                                                      _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T), int(N),
+                                                      int(env_episode_length), int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)),
+                                                      int(counter) & (2 ** 64 - 1), int(bool(centralized)), _stream())
+    _lib.check(rc, "mappo_rollout_episode_world_comm")
+
+
 def rollout_episode_push(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
                          deterministic, counter, centralized):
     """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_push env in one launch, env steps included

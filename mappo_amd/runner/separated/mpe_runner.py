@@ -20,8 +20,13 @@ mappo_rollout_episode_push, MAPPO_PUSH_EPISODE=0; and the GPU-resident simple_cr
 
 One agent may be MultiDiscrete among Discrete ones where the env declares `accepts_multidiscrete_agents` (the GPU-resident
 simple_world_comm: its leader moves and speaks): that agent's buffer carries [T, N, K] actions and log-probs, `collect` keeps all K
-columns, `pack_actions` builds what the env takes, and every agent collects through collect_into — neither mappo_rollout_step nor a
-one-launch episode covers such a run."""
+columns, `pack_actions` builds what the env takes, and every agent collects through collect_into — mappo_rollout_step does not
+cover such a run.  Its one-launch episode (mappo_rollout_episode_world_comm) is OPT-IN, MAPPO_WORLD_COMM_EPISODE=1 (the env's
+`episode_default` is "0"): the launch samples through tile16r_step, collect_into through mlp_forward_kernel, and the two do not
+round alike, so the default stays what it was.  That launch runs the six actors and the environments only (the env declares
+`episode_critics_after`): each critic then runs ONCE on the agent's share_obs viewed as [(T + 1) N, S] — the wide kernels at the
+centralized S = 192 — straight into value_preds, slot T being the bootstrap value, and the GAE scan follows: 1 + 6 + 6 launches
+where the stepwise path has about 490.  Recurrent policies, layer_N = 2 or the flag unset keep the stepwise path."""
 import os
 import time
 
@@ -175,14 +180,16 @@ class MPERunner(Runner):
             b.share_obs[0].copy_(share if self.use_centralized_V else obs[agent_id])
             b.obs[0].copy_(obs[agent_id])
 
-    # ---- one rollout episode in one launch (env.episode_launch: mappo_rollout_episode_comm / _adversary / _tag / _push / _crypto) ----
+    # ---- one rollout episode in one launch (env.episode_launch: mappo_rollout_episode_comm / _adversary / _tag / _push / _crypto /
+    # _world_comm) ----
     def _episode_ready(self):
-        """The env is GPU-resident and steps inside the launch (it has episode_launch, and its env variable episode_flag is not "0"),
+        """The env is GPU-resident and steps inside the launch (it has episode_launch, and its env variable episode_flag — where unset,
+        the env's episode_default, "1" unless it says otherwise — is not "0"),
         the policies are what its kernel is built for (feed-forward, narrow, layer_N <= 1, one layer_N and activation in all
         networks, the env's own widths) and the buffers have the device layout the launch writes.  Anything else takes the stepwise
         path."""
         env = self.envs
-        if not hasattr(env, "episode_launch") or os.environ.get(env.episode_flag, "1") == "0" or self.num_agents != env.M:
+        if not hasattr(env, "episode_launch") or os.environ.get(env.episode_flag, getattr(env, "episode_default", "1")) == "0" or self.num_agents != env.M:
             return False
         return self._episode_shapes_ready(env, env.episode.device)
 
@@ -190,7 +197,15 @@ class MPERunner(Runner):
 
     def _episode_shapes_ready(self, env, dev):
         """dev: where the env's tensors landed."""
-        if not self._fused_ff():
+        after = bool(getattr(env, "episode_critics_after", False))
+        if after:
+            # the launch runs the actors alone and the critics follow on the host (a MultiDiscrete head and a 192-wide critic are
+            # not _fused_ff): feed-forward networks, the critic sharing the actor's layer_N and activation
+            if not self._ragged or any(p.actor.desc.recurrent or p.critic.desc.recurrent
+                                       or (p.critic.desc.layer_N, p.critic.desc.use_relu) != (p.actor.desc.layer_N, p.actor.desc.use_relu)
+                                       for p in self.policy):
+                return False
+        elif not self._fused_ff():
             return False
         d0 = self.policy[0].actor.desc
         S = sum(env.obs_dims)
@@ -207,8 +222,9 @@ class MPERunner(Runner):
 
     @torch.no_grad()
     def _collect_episode(self, deterministic=False):
-        """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent."""
-        N = self.n_rollout_threads
+        """T x (collect, env.step, insert) + compute() as one launch + one GAE scan per agent — and, where the env's launch leaves the
+        critics out (episode_critics_after), one critic forward per agent over all T + 1 slots in between."""
+        N, T = self.n_rollout_threads, self.episode_length
         if self._next_values is None:
             self._next_values = [torch.empty(N, device=self.device) for _ in range(self.num_agents)]
         from mappo_amd import ops
@@ -216,10 +232,14 @@ class MPERunner(Runner):
                               b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds, self._next_values[agent_id])
                for agent_id, (p, b) in enumerate(zip(self.policy, self.buffer))]
         self.envs.episode_launch(ags, self.episode_length, deterministic, 0, self.use_centralized_V)
+        after = bool(getattr(self.envs, "episode_critics_after", False))
         for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
             b.step = 0
             tr.prep_rollout()
-            b.compute_returns(self._next_values[agent_id], tr.value_normalizer)
+            if after:                                               # get_values' forward, once: slot T is the bootstrap value
+                rows = (T + 1) * N
+                tr.policy.critic(b.share_obs.view(rows, -1), b.rnn_states_critic[-1], b.masks[-1], out=b.value_preds.view(rows, 1))
+            b.compute_returns(b.value_preds[T].view(N) if after else self._next_values[agent_id], tr.value_normalizer)
 
     @torch.no_grad()
     def compute(self):

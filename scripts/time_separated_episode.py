@@ -7,8 +7,8 @@
     push       SimplePushVecEnv (adversary 8 -> 5, good agent 19 -> 5, the two collide, per-agent rewards)
     crypto     SimpleCryptoVecEnv (Eve 4 -> 4, Bob and Alice 8 -> 4, nobody moves, per-agent rewards)
     world_comm SimpleWorldCommVecEnv (leader 34 -> MultiDiscrete (5, 4), three adversaries 34 -> 5, two good agents 28 -> 5, 192-wide
-               centralized critics, per-agent rewards): stepwise only, through collect_into — the env has no episode_launch, and this
-               is the baseline a one-launch episode for it will be judged against
+               centralized critics, per-agent rewards): stepwise through collect_into (this env's path is opt-in, so its baseline runs with
+               MAPPO_WORLD_COMM_EPISODE unset); episode = mappo_rollout_episode_world_comm + one critic forward per agent
 
     stepwise   T x (one mappo_rollout_step per agent + the env's step launch + the agents' inserts) + one bootstrap launch per agent,
                launched from Python (the env's episode_flag, e.g. MAPPO_TAG_EPISODE, = 0)
@@ -58,7 +58,9 @@ def main(out, scenario, N, rollouts):
     res = []
     one_launch = hasattr(env_cls, "episode_launch")
     for name, flag in (("stepwise", "0"), ("episode", "1")) if one_launch else (("stepwise", "0"),):
-        if one_launch:
+        if one_launch and flag == getattr(env_cls, "episode_default", None):
+            os.environ.pop(env_cls.episode_flag, None)              # an opt-in env's baseline is the flag UNSET: what a default run does
+        elif one_launch:
             os.environ[env_cls.episode_flag] = flag
         r = runner(env_cls, N, T)
         assert r._episode_ready() == (flag == "1")
