@@ -33,7 +33,8 @@ typedef void *mappo_stream_t; /* hipStream_t */
 #define MAPPO_ENOTIMPL (-3)  /* valid in the reference but not built here (e.g. popart) */
 
 #define MAPPO_HIDDEN 64      /* hidden_size the MFMA kernels are tiled for (config.py:199 default) */
-#define MAPPO_MAX_IN_DIM 512 /* obs / share_obs width */
+#define MAPPO_MAX_IN_DIM 2048 /* obs / share_obs width (Discrete action spaces; 65..512: the tuned wide kernels, 513..2048: the
+                               * sliced layer-1 kernels — the entry points that stay at 512 or 64 say so below and refuse by name) */
 #define MAPPO_MAX_ACTIONS 32 /* Discrete(n) with n <= 32 */
 #define MAPPO_MAX_LAYER_N 2
 
@@ -248,7 +249,7 @@ int mappo_mlp_backward(const float *params, const mappo_net_desc *desc /*host*/,
                        float *slabs, int64_t slab_stride, int64_t slab_col0,
                        float *wide_ws /*in_dim > 64: mappo_wide_workspace_floats(B) floats, else NULL*/,
                        mappo_stream_t stream);
-/* Wide observations (64 < in_dim <= 512; reference: mlp.py:18-55 with a wide input layer): the update / backward launches
+/* Wide observations (64 < in_dim <= MAPPO_MAX_IN_DIM = 2048; up to 512 the tuned kernels, beyond them layer 1 in K slices; reference: mlp.py:18-55 with a wide input layer): the update / backward launches
  * run layer 1 as their own MFMA kernel and leave d z1 plus the per-row LayerNorm statistics in `wide_ws`;
  * mappo_wide_l1_backward then produces the W1 and feature-norm gradient columns (one slab row per workgroup of its grid.x,
  * mappo_wide_l1_slabs(B) rows).  The workspace has one of two layouts, a PURE function of the descriptor and of which
@@ -857,6 +858,8 @@ int mappo_synth_smac_step(float *obs, float *share_obs, float *avail, float *rew
 #define MAPPO_PROF_SLAB_REDUCE 4
 #define MAPPO_PROF_ADAM 5
 #define MAPPO_PROF_ACT 6
+#define MAPPO_PROF_WIDE_L1 7 /* layer 1 of a wide-input update: its forward inside mappo_*_update / mappo_trunk_backward, its weight
+                              * gradient inside mappo_wide_l1_backward (in_dim > 64) */
 #define MAPPO_PROF_COUNT 8
 int mappo_profile_arm(int32_t kernel_id, void *ev_start /*hipEvent_t*/, void *ev_stop /*hipEvent_t*/);
 

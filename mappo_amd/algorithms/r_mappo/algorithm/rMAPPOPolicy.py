@@ -142,7 +142,7 @@ class R_MAPPOPolicy:
 
     def can_fuse_step(self):
         a, c = self.actor.desc, self.critic.desc
-        same_class = (a.in_dim <= 64) == (c.in_dim <= 64) and max(a.in_dim, c.in_dim) <= 512       # both narrow or both wide
+        same_class = (a.in_dim <= 64) == (c.in_dim <= 64) and max(a.in_dim, c.in_dim) <= 512       # both narrow or both wide; 513..2048: one launch per network (collect_into)
         return (not a.recurrent and not c.recurrent and same_class and a.layer_N == c.layer_N and a.use_relu == c.use_relu)
 
     @torch.no_grad()

@@ -58,6 +58,9 @@ class _MultiActShell(nn.Module):
         self.action_outs = nn.ModuleList(outs)
 
 
+MAX_IN_DIM = 2048          # MAPPO_MAX_IN_DIM (include/mappo_hip.h): 65..512 the tuned wide kernels, 513..2048 layer 1 in K slices
+
+
 def _check_supported(args):
     if args.use_popart:
         raise NotImplementedError("use_popart: PopArt.update raises in the reference itself (SURVEY.md §8c)")
@@ -73,6 +76,8 @@ class _NetBase(nn.Module):
 
     def _setup(self, args, in_dim, out_dim, head_prefix, flat, device):
         _check_supported(args)
+        if in_dim > MAX_IN_DIM:
+            raise NotImplementedError(f"input width {in_dim}: the layer-1 kernels take in_dim <= {MAX_IN_DIM} (MAPPO_MAX_IN_DIM)")
         self.hidden_size = args.hidden_size
         self._recurrent = bool(args.use_naive_recurrent_policy or args.use_recurrent_policy)
         self._recurrent_N = args.recurrent_N

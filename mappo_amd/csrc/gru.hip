@@ -444,6 +444,8 @@ extern "C" int mappo_recurrent_rollout_step(const float *actor_params, const map
   ins.mask_dst = dst->masks; ins.bad_dst = dst->bad_masks; ins.active_dst = dst->active_masks; ins.ha_dst = dst->rnn_states;
   ins.hc_dst = dst->rnn_states_critic; ins.N = N; ins.M = M; ins.D = actor_desc->in_dim; ins.S = critic_desc->in_dim;
   ins.A = actor_desc->out_dim; ins.H = HID;
+  MAPPO_REQUIRE(actor_desc->in_dim <= 512 && critic_desc->in_dim <= 512, "recurrent_rollout_step: in_dim %d / %d > 512 (wider networks take "
+                "mappo_mlp_features + mappo_gru_step_dual)", actor_desc->in_dim, critic_desc->in_dim);
   if (actor_desc->in_dim > 64 && critic_desc->in_dim > 64)
     return mappo_recurrent_step_dual_wide_(actor_params, actor_desc, obs, actor_h, actor_h_next, critic_params, critic_desc, share_obs, critic_h,
                                            critic_h_next, nullptr, Nc, avail, deterministic, seed, counter, counter_dev, actions, logp, values, &ins,

@@ -37,6 +37,8 @@ static int launch_forward(const FwdArgs &a_in, hipStream_t st, const char *who) 
   int64_t nb = (n_tiles + nw - 1) / nw;
   if (nb > NUM_CU) nb = NUM_CU;
   dim3 grid((unsigned)nb), block(WAVE * nw);
+  // beyond the tuned wide kernels: layer 1 in K slices + the register-resident tail, one launch (mlp_wide_sliced.h)
+  if (a.desc.in_dim > WIDE_TUNED_MAX_D) return wide_sliced_forward(MODE, a, st, who);
   {
     if (a.desc.in_dim > MAXD && a.desc.in_dim <= 512 && a.x_M == 0) {
       // wide inputs: layer 1 from registers + double-buffered W1 chunks, the rest of the network on the same tile (mlp_wide16.h)
@@ -181,7 +183,7 @@ static int upd16_tile_cost(const mappo_net_desc &d, bool actor) {
 }
 // trunk backward (gradient arriving at the trunk output; recurrent networks): same kernels, no head
 static bool upd16_trunk_eligible(const mappo_net_desc &d) {
-  return d.in_dim <= 512 && d.layer_N <= 1;
+  return d.in_dim <= MAPPO_MAX_IN_DIM && d.layer_N <= 1;
 }
 static size_t upd16_trunk_lds_floats(const mappo_net_desc &d) {
   if (d.in_dim > MAXD) return d.layer_N > 0 ? L16<1, 3, true, true>::TOTAL : L16<0, 3, true, true>::TOTAL;
@@ -191,7 +193,7 @@ static size_t upd16_trunk_lds_floats(const mappo_net_desc &d) {
 }
 // ---- wide inputs through the 16-sample-tile kernels ----
 static bool upd16x_eligible(const mappo_net_desc &d, bool actor) {
-  return d.in_dim > MAXD && d.in_dim <= 512 && d.layer_N <= 1 && !d.recurrent && (actor ? d.out_dim <= 16 : d.out_dim == 1);
+  return d.in_dim > MAXD && d.in_dim <= MAPPO_MAX_IN_DIM && d.layer_N <= 1 && !d.recurrent && (actor ? d.out_dim <= 16 : d.out_dim == 1);
 }
 static int64_t wide_z1_offset(int64_t B) { return wide16_z1_offset(B); }     // workspace layout: mlp_wide16.h (>= the [64][B] | mean0 | rstd0 of the round-1 kernels)
 
@@ -224,7 +226,17 @@ static int prep16(Upd16Args &a, bool actor, bool wide, const char *who) {
   a.zero_row0 = a.zero_row1 = 0; a.zero_col0 = 0; a.zero_cols = 0; a.zero_partials = nullptr;
   return MAPPO_OK;
 }
-// z1 = b1' + W1' xhat0 and the row statistics, one launch (mlp_wide16.h)
+// layer 1 of the 16-sample-tile update path in K slices (mlp_wide_sliced.h): beyond the tuned kernels' 512 columns, and only there.
+// Experiment build -DWIDE_EXP_SLICED (scripts/exp_build.py, never the product library): MAPPO_WIDE_SLICED=1 then takes it at every
+// wide width, for the A/B against the tuned kernels in DESIGN.md §5.
+static bool wide_sliced_l1(int in_dim) {
+#ifdef WIDE_EXP_SLICED
+  static const bool forced = getenv("MAPPO_WIDE_SLICED") && atoi(getenv("MAPPO_WIDE_SLICED")) != 0;
+  if (forced && in_dim > MAXD) return true;
+#endif
+  return in_dim > WIDE_TUNED_MAX_D;
+}
+// z1 = b1' + W1' xhat0 and the row statistics, one launch (mlp_wide16.h; beyond its 512 columns mlp_wide_sliced.h)
 static int launch_wide_l1_fwd(const float *params, const mappo_net_desc &d, const NetOff &o, const float *x, const int32_t *rows, int64_t B,
                               float *z1, float *mean0, float *rstd0, hipStream_t st, const char *who) {
   Wide16Args w = {};
@@ -232,7 +244,10 @@ static int launch_wide_l1_fwd(const float *params, const mappo_net_desc &d, cons
   w.w1 = o.w1; w.b1 = o.b1; w.fn_w = d.use_feature_norm ? o.fn_w : -1; w.fn_b = d.use_feature_norm ? o.fn_b : -1;
   const int64_t n_groups = ((B + 15) / 16 + 7) / 8;
   dim3 grid((unsigned)(n_groups < NUM_CU ? n_groups : NUM_CU));
-  if (int rcl = wide16_launch_l1_fwd(w, grid, st)) return rcl;
+  if (wide_sliced_l1(d.in_dim)) {
+    const dim3 gs((unsigned)(n_groups < 2 * NUM_CU ? n_groups : 2 * NUM_CU));      // (workgroups stride over the tile groups; 200 VGPRs: one resident per CU)
+    if (int rcl = wide_sliced_launch_l1_fwd(w, gs, st)) return rcl;
+  } else if (int rcl = wide16_launch_l1_fwd(w, grid, st)) return rcl;
   MAPPO_CHECK_LAUNCH(who);
   return MAPPO_OK;
 }
@@ -365,7 +380,7 @@ extern "C" int mappo_trunk_backward_seq(const float *params, const mappo_net_des
                                         int64_t slab_col0, float *wide_ws, mappo_stream_t stream) {
   if (int rc = check_desc_trunk(desc, "trunk_backward_seq")) return rc;
   MAPPO_REQUIRE(params && x && dx_blocked && slabs && L > 0 && Nc > 0, "trunk_backward_seq: bad arguments");
-  MAPPO_REQUIRE(desc->in_dim <= 512 && desc->layer_N <= 1, "trunk_backward_seq: in_dim %d / layer_N %d take mappo_trunk_backward", desc->in_dim, desc->layer_N);
+  MAPPO_REQUIRE(desc->in_dim <= 512 && desc->layer_N <= 1, "trunk_backward_seq: in_dim %d > 512 or layer_N %d > 1 take mappo_trunk_backward", desc->in_dim, desc->layer_N);
   MAPPO_REQUIRE(desc->in_dim <= MAXD || (Nc & 15) == 0, "trunk_backward_seq: wide inputs need Nc %% 16 == 0 (Nc = %d)", Nc);
   UpdArgs a = {};
   a.params = params; a.x = x; a.rows = rows; a.dHT = dx_blocked; a.slabs = slabs; a.slab_stride = slab_stride;
@@ -760,7 +775,6 @@ extern "C" int mappo_wide_l1_backward(const float *params, const mappo_net_desc 
   MAPPO_REQUIRE(params && x && wide_ws && slabs && B > 0, "wide_l1_backward: bad arguments");
   MAPPO_REQUIRE(layout == MAPPO_WIDE_LAYOUT_BLOCKED || layout == MAPPO_WIDE_LAYOUT_FEATURE_MAJOR,
                 "wide_l1_backward: layout %d (pass mappo_wide_layout(desc, producer) of the launch that filled the workspace)", (int)layout);
-  MAPPO_REQUIRE(layout != MAPPO_WIDE_LAYOUT_BLOCKED || desc->in_dim <= 512, "wide_l1_backward: the blocked layout exists for in_dim <= 512 only");
   {
     if (layout == MAPPO_WIDE_LAYOUT_BLOCKED) {
       // 16x16x4 kernel (mlp_wide16.h): raw products, every input element read once
@@ -772,6 +786,13 @@ extern "C" int mappo_wide_l1_backward(const float *params, const mappo_net_desc 
       const int nch = (desc->in_dim + 63) / 64;
       w.nca = nch <= 2 ? 2 : (nch <= 4 ? 4 : 8);
       const int rows_max = mappo_mlp_backward_slabs(B);
+      if (wide_sliced_l1(desc->in_dim)) {
+        // 512-column slices side by side (mlp_wide_sliced.h): one workgroup per (slab row, slice), every slab row written
+        w.nca = 8; w.groups = 1;
+        if (int rcl = wide_sliced_launch_l1_bwd(w, dim3((unsigned)rows_max, (unsigned)((nch + 7) / 8)), as_stream(stream))) return rcl;
+        MAPPO_CHECK_LAUNCH("wide_l1_backward");
+        return MAPPO_OK;
+      }
       w.groups = 8 / w.nca;
       if (rows_max < w.groups) w.groups = 1;
       const int gx = rows_max / w.groups;

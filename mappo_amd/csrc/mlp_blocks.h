@@ -17,15 +17,17 @@
 // is applied when the tile is read as an operand (two broadcast LDS reads + one FMA per MFMA pair), so the backward pass finds
 // xhat in the tile and only mean/rstd/sign-mask (3 registers) survive from the forward.
 //
-// Which kernel family serves which shape (hidden == 64, out_dim <= 32, layer_N <= 2, in_dim <= 512):
+// Which kernel family serves which shape (hidden == 64, out_dim <= 32, layer_N <= 2, in_dim <= 2048):
 //
 //   forward   mlp_forward_kernel (mlp_fwd.h)                    in_dim <= 64: mappo_mlp_forward / mappo_actor_act
 //             features16 / rollout step / episode (mlp_fwd16.h) in_dim <= 64, weights in registers, 16-sample tiles
 //             wide_forward16* (mlp_wide16.h)                    in_dim 65..512
+//             wide_forward_sliced (mlp_wide_sliced.h)           in_dim 513..2048
 //   update    upd16   one wave per 16-sample tile (mlp_upd16.h)     in_dim <= 64, layer_N <= 1, actor out_dim <= 16, LDS layout fits
 //             upd16x  the same from z1 on, layer 1 in mlp_wide16.h  in_dim 65..512, layer_N <= 1, actor out_dim <= 16
+//                     (in_dim 513..2048: layer 1 in mlp_wide_sliced.h)
 //             upd2    pair kernel (mlp_upd2.h)                      in_dim <= 64 otherwise
-//             wide    K-chunked kernel (mlp_upd.h)                  in_dim 65..512 otherwise (layer_N = 2, external head gradient)
+//             wide    K-chunked kernel (mlp_upd.h)                  in_dim 65..2048 otherwise (layer_N = 2, external head gradient)
 //   The dual launch takes upd16d (both networks upd16) or upd2d (the pair kernel for both).  The dispatch itself is launch_update
 //   and mappo_actor_critic_update in mlp.hip; the limits and the cross-unit launchers are declared in mlp_launch.h.
 #pragma once

@@ -109,4 +109,14 @@ struct WideStepIO {
 int wide16_launch_recurrent_step_dual(bool relu, int ln, size_t lds_bytes, hipStream_t st, const Wide16Args &wa, const FwdArgs &a,
                                       const Wide16Args &wc, const FwdArgs &c, int nt16, const WideStepIO &io);
 
+// ---- inputs beyond the tuned wide kernels' 512 columns (mlp_wide_sliced.h), defined in mlp_wide_sliced.hip / mlp_wide_sliced_r{0,1}.hip ----
+#define WIDE_TUNED_MAX_D 512           // widest input of the kernels in mlp_wide16.h; above it (up to MAPPO_MAX_IN_DIM) the sliced kernels
+int wide_sliced_launch_l1_fwd(const Wide16Args &w, dim3 grid, hipStream_t st);
+int wide_sliced_launch_l1_bwd(const WideBwd16Args &w, dim3 grid, hipStream_t st);      // grid: (slab rows, 512-column slices)
+template <bool R>
+int wide_sliced_launch_forward_r(int mode, int ln, dim3 grid, size_t lds_bytes, hipStream_t st, const Wide16Args &w, const FwdArgs &a,
+                                 const char *who);
+// the whole forward of one network (a.x_M / x_sn / x_sm: strided rows); mode 0: head output, 1: get_actions, 2: trunk features [64][B]
+int wide_sliced_forward(int mode, const FwdArgs &a, hipStream_t st, const char *who);
+
 int launch_features16(const FwdArgs &a_in, hipStream_t st);      // mlp_step.hip

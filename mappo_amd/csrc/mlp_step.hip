@@ -28,12 +28,22 @@ extern "C" int mappo_mlp_features_dual(const float *params_a, const mappo_net_de
                                        int64_t B, mappo_stream_t stream) {
   if (int rc = check_desc_trunk(desc_a, "mlp_features_dual")) return rc;
   if (int rc = check_desc_trunk(desc_c, "mlp_features_dual")) return rc;
-  MAPPO_REQUIRE((desc_a->in_dim <= MAXD) == (desc_c->in_dim <= MAXD) && desc_a->in_dim <= 512 && desc_c->in_dim <= 512,
-                "mlp_features_dual: both networks narrow (in_dim <= %d) or both wide (<= 512)", MAXD);
+  const bool sliced = desc_a->in_dim > WIDE_TUNED_MAX_D && desc_c->in_dim > WIDE_TUNED_MAX_D;
+  MAPPO_REQUIRE(sliced || ((desc_a->in_dim <= MAXD) == (desc_c->in_dim <= MAXD) && desc_a->in_dim <= 512 && desc_c->in_dim <= 512),
+                "mlp_features_dual: both networks narrow (in_dim <= %d), both wide (65..512) or both beyond 512 (in_dim %d / %d: run "
+                "mappo_mlp_features per network)", MAXD, desc_a->in_dim, desc_c->in_dim);
   MAPPO_REQUIRE(desc_a->layer_N == desc_c->layer_N && desc_a->use_relu == desc_c->use_relu,
                 "mlp_features_dual: the networks must share layer_N and the activation");
   MAPPO_REQUIRE(params_a && x_a && featT_a && params_c && x_c && featT_c && B > 0, "mlp_features_dual: bad arguments");
   MAPPO_CLEAR_STICKY();
+  if (sliced) {
+    // beyond the tuned wide kernels: each network's one-launch sliced forward (mlp_wide_sliced.h), one after the other
+    FwdArgs a = {}, c = {};
+    a.params = params_a; a.x = x_a; a.out = featT_a; a.desc = *desc_a; a.B = B;
+    c.params = params_c; c.x = x_c; c.out = featT_c; c.desc = *desc_c; c.B = B;
+    if (int rc = wide_sliced_forward(2, a, as_stream(stream), "mlp_features_dual")) return rc;
+    return wide_sliced_forward(2, c, as_stream(stream), "mlp_features_dual");
+  }
   if (desc_a->in_dim > MAXD) {
     // wide inputs: the one-launch wide forward (mlp_wide16.h) of both networks by workgroup role
     FwdArgs a = {}, c = {};
@@ -123,8 +133,10 @@ static int rollout_step_impl(const float *actor_params, const mappo_net_desc *ac
                              float *mask_dst, int32_t centralized, mappo_stream_t stream, const MdHeads *md) {
   if (int rc = check_desc(actor_desc, "rollout_step")) return rc;
   if (int rc = check_desc(critic_desc, "rollout_step")) return rc;
-  MAPPO_REQUIRE((actor_desc->in_dim <= MAXD) == (critic_desc->in_dim <= MAXD) && actor_desc->in_dim <= 512 && critic_desc->in_dim <= 512,
-                "rollout_step: both networks narrow (in_dim <= %d) or both wide (<= 512)", MAXD);
+  const bool sliced = actor_desc->in_dim > WIDE_TUNED_MAX_D && critic_desc->in_dim > WIDE_TUNED_MAX_D;
+  MAPPO_REQUIRE(sliced || ((actor_desc->in_dim <= MAXD) == (critic_desc->in_dim <= MAXD) && actor_desc->in_dim <= 512 && critic_desc->in_dim <= 512),
+                "rollout_step: both networks narrow (in_dim <= %d), both wide (65..512) or both beyond 512 (in_dim %d / %d: run "
+                "mappo_actor_act and mappo_mlp_forward per network)", MAXD, actor_desc->in_dim, critic_desc->in_dim);
   MAPPO_REQUIRE(actor_desc->layer_N == critic_desc->layer_N && actor_desc->use_relu == critic_desc->use_relu,
                 "rollout_step: actor and critic must share layer_N and the activation");
   MAPPO_REQUIRE(critic_desc->out_dim == 1, "rollout_step: critic out_dim must be 1");
@@ -133,6 +145,25 @@ static int rollout_step_impl(const float *actor_params, const mappo_net_desc *ac
   MAPPO_REQUIRE(M > 0 || !obs_dst, "rollout_step: the fused insert needs the (thread, agent) row layout (M > 0)");
   MAPPO_REQUIRE(!obs_dst || (share_dst && rewards && dones && rew_dst && mask_dst && B % M == 0), "rollout_step: incomplete insert arguments");
   MAPPO_CLEAR_STICKY();
+  if (sliced) {
+    // beyond the tuned wide kernels: the insert as its own launch, then each network's one-launch sliced forward (mlp_wide_sliced.h)
+    // reading the env's rows in place
+    if (obs_dst)
+      if (int rci = mappo_insert_mpe(obs, obs_stride_n, obs_stride_m, rewards, rew_stride_n, rew_stride_m, dones, done_stride_n, done_stride_m,
+                                     obs_dst, share_dst, rew_dst, mask_dst, (int32_t)(B / M), M, actor_desc->in_dim, centralized, stream))
+        return rci;
+    if (actions) {
+      FwdArgs a = {};
+      a.params = actor_params; a.x = obs; a.avail = avail; a.actions = actions; a.logp = logp; a.desc = *actor_desc; a.B = B;
+      a.deterministic = deterministic; a.seed = seed; a.counter = counter; a.counter_dev = counter_dev;
+      a.x_M = M; a.x_sn = obs_stride_n; a.x_sm = obs_stride_m;
+      if (int rc = wide_sliced_forward(1, a, as_stream(stream), "rollout_step")) return rc;
+    }
+    FwdArgs c = {};
+    c.params = critic_params; c.x = share_obs; c.out = values; c.desc = *critic_desc; c.B = B;
+    c.x_M = M; c.x_sn = share_stride_n; c.x_sm = share_stride_m;
+    return wide_sliced_forward(0, c, as_stream(stream), "rollout_step");
+  }
   if (actor_desc->in_dim > MAXD) {
     // Wide inputs: the insert is its own (HBM-bound: it moves the rows it copies once in, twice out) launch, the two networks share
     // one (wide_rollout_step_kernel: every CU busy for one chunk-latency chain instead of half the chip for two).

@@ -1,4 +1,4 @@
-// mlp_upd.h — mlp_update_kernel, the K-chunked update kernel for wide inputs (in_dim 65..512) where the 16-sample-tile kernels
+// mlp_upd.h — mlp_update_kernel, the K-chunked update kernel for wide inputs (in_dim 65..2048: it walks any number of 64-column chunks) where the 16-sample-tile kernels
 // do not apply: layer_N = 2 and the external-gradient head of mappo_mlp_backward.  One wave per 32-sample tile; the workgroup
 // streams 64-column chunks of W1 through LDS, each wave re-normalises its rows chunk by chunk; dz1 and the row statistics go to a
 // feature-major HBM scratch from which wide_l1_bwd_kernel (mlp.hip) computes the W1 / feature-norm gradients.  The forward is

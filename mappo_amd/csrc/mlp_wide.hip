@@ -10,13 +10,13 @@ int wide16_launch_l1_fwd(const Wide16Args &w, dim3 grid, hipStream_t st) {
   const size_t lds_bytes = sizeof(float) * ((size_t)HID * 64 * nch + HID);            // W1' whole (fragment order) + folded bias
   const dim3 block(512);
   switch (nch) {
-    case 2: return launch_kernel<wide_l1_fwd16_kernel<2>, WIDE_LDS_WHOLE>("wide_l1_fwd", grid, block, lds_bytes, st, w);
-    case 3: return launch_kernel<wide_l1_fwd16_kernel<3>, WIDE_LDS_WHOLE>("wide_l1_fwd", grid, block, lds_bytes, st, w);
-    case 4: return launch_kernel<wide_l1_fwd16_kernel<4>, WIDE_LDS_WHOLE>("wide_l1_fwd", grid, block, lds_bytes, st, w);
-    case 5: return launch_kernel<wide_l1_fwd16_kernel<5>, WIDE_LDS_WHOLE>("wide_l1_fwd", grid, block, lds_bytes, st, w);
-    case 6: return launch_kernel<wide_l1_fwd16_kernel<6>, WIDE_LDS_WHOLE>("wide_l1_fwd", grid, block, lds_bytes, st, w);
-    case 7: return launch_kernel<wide_l1_fwd16_kernel<7>, WIDE_LDS_WHOLE>("wide_l1_fwd", grid, block, lds_bytes, st, w);
-    default: return launch_kernel<wide_l1_fwd16_kernel<8>, WIDE_LDS_WHOLE>("wide_l1_fwd", grid, block, lds_bytes, st, w);
+    case 2: return launch_kernel<wide_l1_fwd16_kernel<2>, WIDE_LDS_WHOLE, MAPPO_PROF_WIDE_L1>("wide_l1_fwd", grid, block, lds_bytes, st, w);
+    case 3: return launch_kernel<wide_l1_fwd16_kernel<3>, WIDE_LDS_WHOLE, MAPPO_PROF_WIDE_L1>("wide_l1_fwd", grid, block, lds_bytes, st, w);
+    case 4: return launch_kernel<wide_l1_fwd16_kernel<4>, WIDE_LDS_WHOLE, MAPPO_PROF_WIDE_L1>("wide_l1_fwd", grid, block, lds_bytes, st, w);
+    case 5: return launch_kernel<wide_l1_fwd16_kernel<5>, WIDE_LDS_WHOLE, MAPPO_PROF_WIDE_L1>("wide_l1_fwd", grid, block, lds_bytes, st, w);
+    case 6: return launch_kernel<wide_l1_fwd16_kernel<6>, WIDE_LDS_WHOLE, MAPPO_PROF_WIDE_L1>("wide_l1_fwd", grid, block, lds_bytes, st, w);
+    case 7: return launch_kernel<wide_l1_fwd16_kernel<7>, WIDE_LDS_WHOLE, MAPPO_PROF_WIDE_L1>("wide_l1_fwd", grid, block, lds_bytes, st, w);
+    default: return launch_kernel<wide_l1_fwd16_kernel<8>, WIDE_LDS_WHOLE, MAPPO_PROF_WIDE_L1>("wide_l1_fwd", grid, block, lds_bytes, st, w);
   }
 }
 
@@ -33,8 +33,8 @@ int wide16_launch_features_dual(bool relu, int ln, dim3 grid, dim3 block, size_t
 
 template <bool FN, bool GATHER>
 static void wide16_l1_bwd_one(const WideBwd16Args &w, dim3 grid, hipStream_t st) {
-  if ((w.D & 63) == 0) hipLaunchKernelGGL((wide_l1_bwd16_kernel<FN, GATHER, true>), grid, dim3(512), 0, st, w);      // whole chunks: branch-free tile loop
-  else hipLaunchKernelGGL((wide_l1_bwd16_kernel<FN, GATHER, false>), grid, dim3(512), 0, st, w);
+  if ((w.D & 63) == 0) PROF_LAUNCH(MAPPO_PROF_WIDE_L1, (wide_l1_bwd16_kernel<FN, GATHER, true>), grid, dim3(512), 0, st, w);      // whole chunks: branch-free tile loop
+  else PROF_LAUNCH(MAPPO_PROF_WIDE_L1, (wide_l1_bwd16_kernel<FN, GATHER, false>), grid, dim3(512), 0, st, w);
 }
 int wide16_launch_l1_bwd(const WideBwd16Args &w, dim3 grid, hipStream_t st) {
   const bool fn = w.fn_w >= 0;

@@ -789,7 +789,7 @@ def selftest_mfma(A, Bm, D):
 
 
 # ---- measurement hook -----------------------------------------------------------------------------
-PROF_IDS = dict(gae=0, ppo_loss=1, mlp_fwd=2, mlp_bwd=3, slab_reduce=4, adam=5, act=6)
+PROF_IDS = dict(gae=0, ppo_loss=1, mlp_fwd=2, mlp_bwd=3, slab_reduce=4, adam=5, act=6, wide_l1=7)
 
 
 def profile_arm(kernel, start_event, stop_event):

@@ -88,7 +88,7 @@ def can_step_dual(actor, critic):
     """Both networks recurrent with inputs of the same class (<= 64 wide, or 65..512) and the same trunk shape: their rollout
     step runs as two dual launches."""
     da, dc = actor.desc, critic.desc
-    same_class = (da.in_dim <= 64) == (dc.in_dim <= 64) and max(da.in_dim, dc.in_dim) <= 512      # both narrow or both wide
+    same_class = (da.in_dim <= 64) == (dc.in_dim <= 64) and max(da.in_dim, dc.in_dim) <= 512      # both narrow or both wide; 513..2048: mlp_features + gru_forward per network
     return (da.recurrent and dc.recurrent and same_class and da.layer_N == dc.layer_N
             and da.use_relu == dc.use_relu and actor._recurrent_N == 1 and critic._recurrent_N == 1)
 
