@@ -304,6 +304,36 @@ int mappo_actor_critic_update(const float *actor_params, const mappo_net_desc *a
                               const float *vn_state, const double *mb_moments, const mappo_ppo_cfg *cfg /*host*/, float *slabs,
                               int64_t slab_stride, int64_t actor_col0, int64_t critic_col0, double *actor_partials,
                               double *critic_partials, mappo_stream_t stream);
+/* The work of n_jobs mappo_actor_critic_update calls — the agents of a separated run (share_policy = False) — in ONE launch.
+ * A job holds exactly that call's arguments (descriptors and cfg by value); jobs may differ in in_dim, out_dim, B, rows and every
+ * pointer.  The grid is the sum of the single calls' grids; every job's slab rows and loss-partial rows [0, mappo_dual_update_slabs)
+ * come out bit for bit as its single call writes them (the same rows written, the same rows zero-filled).  Accepted jobs are
+ * those the single call serves with the 16-sample-tile kernel: both networks feed-forward with in_dim <= 64, Discrete head with
+ * out_dim <= 16, layer_N <= 1 (not the actor with 33..64 inputs and layer_N = 1: pair kernel), and all jobs agree in layer_N,
+ * use_relu and use_feature_norm (the launch is one template instance).  Anything else — n_jobs outside 1..MAPPO_MAX_GROUP, a
+ * NULL pointer, a wide, recurrent or pair-kernel job — returns MAPPO_EINVAL before any launch, naming the job. */
+#define MAPPO_MAX_GROUP 8
+typedef struct mappo_update_job {
+  const float *actor_params;
+  mappo_net_desc actor_desc;
+  const float *obs;
+  const float *critic_params;
+  mappo_net_desc critic_desc;
+  const float *share_obs;
+  const int32_t *rows;       /* or NULL */
+  int64_t B;
+  const float *avail;        /* or NULL */
+  const float *actions, *old_logp, *adv, *active, *v_old, *returns;
+  const float *vn_state;     /* or NULL without use_valuenorm */
+  const double *mb_moments;
+  mappo_ppo_cfg cfg;
+  float *slabs;
+  int64_t slab_stride, actor_col0, critic_col0;
+  double *actor_partials, *critic_partials;
+} mappo_update_job;
+int mappo_actor_critic_update_group(const mappo_update_job *jobs /*host [n_jobs]*/, int32_t n_jobs, mappo_stream_t stream);
+/* 1 if a job with these two descriptors passes the shape checks above (jobs of one launch must also agree with each other), else 0 */
+int32_t mappo_update_group_accepts(const mappo_net_desc *actor_desc /*host*/, const mappo_net_desc *critic_desc /*host*/);
 /* The same two launches for a MultiDiscrete actor (limits and layout: mappo_actor_act_md; r_mappo.py:124-141 with act.py:139-152):
  * actions / old_logp are [.][K] in buffer order.  With r_j = exp(lp_j - old_lp_j) and s_j = min(r_j adv, clip(r_j) adv) the actor's
  * per-workgroup partials are {sum w sum_j s_j, sum w (1/K) sum_j H_j, sum (1/K) sum_j r_j, -}, so mappo_update_stats yields the policy
@@ -466,6 +496,23 @@ int mappo_reduce_clip_adam(const float *slabs, int32_t n_slabs, int64_t slab_str
                            float *exp_avg, float *exp_avg_sq, const int64_t *seg_bounds /*host [n_seg+1]*/, int32_t n_seg,
                            const float *opt_hyper, int32_t *opt_step, float *grad_norms, double *norm_acc /*or NULL*/,
                            void *workspace, mappo_stream_t stream);
+/* n_jobs mappo_reduce_clip_adam calls (1..MAPPO_MAX_GROUP; a job holds that call's arguments, the workspace is per job) in the
+ * same TWO launches: within a job the same reduction order over slab rows, the same norm, clip, Adam and norm_acc, so params,
+ * grad, moments, opt_step and grad_norms equal the single call's bit for bit. */
+typedef struct mappo_optim_job {
+  const float *slabs;
+  int32_t n_slabs;
+  int64_t slab_stride;
+  float *params, *grad, *exp_avg, *exp_avg_sq;
+  int64_t seg_bounds[5];     /* [n_seg + 1], increasing multiples of 256 from 0 */
+  int32_t n_seg;             /* 1..4 */
+  const float *opt_hyper;
+  int32_t *opt_step;
+  float *grad_norms;
+  double *norm_acc;          /* or NULL */
+  void *workspace;           /* mappo_optim_workspace_bytes(seg_bounds[n_seg]) bytes */
+} mappo_optim_job;
+int mappo_reduce_clip_adam_group(const mappo_optim_job *jobs /*host [n_jobs]*/, int32_t n_jobs, mappo_stream_t stream);
 
 /* GPU-vectorised MPE simple_spread (csrc/mpe_env.hip): N environments x M agents x L landmarks, one launch per
  * step.  Replaces World.step / Scenario.reward / Scenario.observation / MultiAgentEnv.step + the vec-env's reset-on-done

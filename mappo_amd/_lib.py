@@ -39,6 +39,25 @@ class CommAgent(C.Structure):
                 [(n, C.c_void_p) for n in ("obs_buf", "share_buf", "rew_buf", "mask_buf", "actions", "logp", "values", "next_values")])
 
 
+MAX_GROUP = 8
+
+
+class UpdateJob(C.Structure):
+    """mappo_update_job: the arguments of one mappo_actor_critic_update call, as a job of mappo_actor_critic_update_group (include/mappo_hip.h)."""
+    _fields_ = ([("actor_params", C.c_void_p), ("actor_desc", NetDesc), ("obs", C.c_void_p), ("critic_params", C.c_void_p), ("critic_desc", NetDesc),
+                 ("share_obs", C.c_void_p), ("rows", C.c_void_p), ("B", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("avail", "actions", "old_logp", "adv", "active", "v_old", "returns", "vn_state", "mb_moments")] +
+                [("cfg", PpoCfg), ("slabs", C.c_void_p), ("slab_stride", C.c_int64), ("actor_col0", C.c_int64), ("critic_col0", C.c_int64),
+                 ("actor_partials", C.c_void_p), ("critic_partials", C.c_void_p)])
+
+
+class OptimJob(C.Structure):
+    """mappo_optim_job: the arguments of one mappo_reduce_clip_adam call, as a job of mappo_reduce_clip_adam_group (include/mappo_hip.h)."""
+    _fields_ = [("slabs", C.c_void_p), ("n_slabs", C.c_int32), ("slab_stride", C.c_int64), ("params", C.c_void_p), ("grad", C.c_void_p),
+                ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("seg_bounds", C.c_int64 * 5), ("n_seg", C.c_int32), ("opt_hyper", C.c_void_p),
+                ("opt_step", C.c_void_p), ("grad_norms", C.c_void_p), ("norm_acc", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 _P, _I32, _I64, _F, _D, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint64
 
 # name -> (restype, argtypes); must list every symbol include/mappo_hip.h declares (tests/test_capi_symbols.py)
@@ -87,6 +106,9 @@ SIGNATURES = {
     "mappo_dual_update_slabs": (_I32, [C.POINTER(NetDesc), C.POINTER(NetDesc), _I64]),
     "mappo_actor_critic_update": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, C.POINTER(NetDesc), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                             C.POINTER(PpoCfg), _P, _I64, _I64, _I64, _P, _P, _P]),
+    "mappo_actor_critic_update_group": (C.c_int, [C.POINTER(UpdateJob), _I32, _P]),
+    "mappo_update_group_accepts": (_I32, [C.POINTER(NetDesc), C.POINTER(NetDesc)]),
+    "mappo_reduce_clip_adam_group": (C.c_int, [C.POINTER(OptimJob), _I32, _P]),
     "mappo_actor_update_md": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, _I64, _P, C.POINTER(_I32), _I32, _P, _P, _P, _P, _P, C.POINTER(PpoCfg),
                                         _P, _I64, _I64, _P, _P, _I32, _P]),
     "mappo_actor_critic_update_md": (C.c_int, [_P, C.POINTER(NetDesc), _P, _P, C.POINTER(NetDesc), _P, _P, _I64, _P, C.POINTER(_I32), _I32,

@@ -385,23 +385,85 @@ class R_MAPPO():
                 else:
                     self._update(src, rows, B, update_actor, moments_ready=glue or (whole and epoch > 0))
         if self._epochs is not None:
-            # (rows of loss partials the update kernels wrote; not taken from a side effect of _update_kernels: under data
-            # parallelism the epochs may have been graph replays, during which no Python runs)
-            n_rows = ops.dual_update_slabs(self.policy.actor.desc, self.policy.critic.desc, S) if (update_actor and self._dual_update and self.policy.can_dual_update()) \
-                else ops.mlp_backward_slabs(S)
-            pairs = buffer.after_update_pairs() if (glue and after_update) else None
-            if pairs:
-                ops.train_epilogue(self._pa if update_actor else None, n_rows, self._pc, n_rows, self._mb_moments, self._cfg,
-                                   self._stats, self._acc, pairs)
-                after_update = False                           # done in that launch
-            else:
-                ops.update_stats(self._pa if update_actor else None, n_rows, self._pc, n_rows, self._mb_moments, self._cfg,
-                                 self._stats, self._acc)
-            self._epochs = None
+            after_update = self._train_epilogue(buffer, S, update_actor, after_update, glue)
         if dp_graph and self._dp_graphs.get(key) is None:
             self._dp_graphs[key] = "warm"                      # first train() ran eagerly: workspaces exist now
         if after_update:
             buffer.after_update()
+
+    def _train_epilogue(self, buffer, S, update_actor, after_update, glue):
+        """The statistics of the epoch-batched mode, in one launch with after_update's copies where the glue is fused; returns
+        whether after_update is still to do."""
+        # (rows of loss partials the update kernels wrote; not taken from a side effect of _update_kernels: under data
+        # parallelism the epochs may have been graph replays, during which no Python runs)
+        n_rows = ops.dual_update_slabs(self.policy.actor.desc, self.policy.critic.desc, S) if (update_actor and self._dual_update and self.policy.can_dual_update()) \
+            else ops.mlp_backward_slabs(S)
+        pairs = buffer.after_update_pairs() if (glue and after_update) else None
+        if pairs:
+            ops.train_epilogue(self._pa if update_actor else None, n_rows, self._pc, n_rows, self._mb_moments, self._cfg,
+                               self._stats, self._acc, pairs)
+            after_update = False                           # done in that launch
+        else:
+            ops.update_stats(self._pa if update_actor else None, n_rows, self._pc, n_rows, self._mb_moments, self._cfg,
+                             self._stats, self._acc)
+        self._epochs = None
+        return after_update
+
+    # ---- the phases of the whole-buffer fused train(), callable one by one -------------------------------------------------
+    # A runner that trains several agents (runner/separated) interleaves them: every agent's prologue, then per epoch ONE grouped
+    # update launch and ONE grouped optimiser call over the agents' jobs (ops.actor_critic_update_group / reduce_clip_adam_group),
+    # then every agent's epilogue.  Per agent the launches' work and order are train()'s own, so the results are bit for bit.
+    def phase_ready(self, update_actor=True):
+        """Whether train() of this trainer IS the sequence the phases below reproduce, with an update the grouped launch takes."""
+        pol = self.policy
+        return bool(update_actor and self._fused and self._dual_update and pol.can_dual_update() and not pol.actor.head_dims
+                    and not (self._use_recurrent_policy or self._use_naive_recurrent) and self.num_mini_batch == 1
+                    and not self._exact_order and self._dist is None and not self._concurrent_update and self._fuse_glue
+                    and os.environ.get("MAPPO_EPOCH_BATCH", "1") != "0" and ops.update_group_accepts(pol.actor.desc, pol.critic.desc))
+
+    def phase_sync(self):
+        """Host-side switches, applied before the launch sequence (and outside a captured graph), as train() does."""
+        self._sync_actor_mode(True)
+
+    @torch.no_grad()
+    def phase_prologue(self, buffer):
+        """Advantages, zeroed accumulators, minibatch moments and the ppo_epoch ValueNorm states (two launches)."""
+        self._epochs = dict(n=self.ppo_epoch, e=0, states=self._buf("vn_states", (self.ppo_epoch, 3)))
+        adv = self._train_prologue(buffer)
+        src, S = self._buffer_sources(buffer, adv)
+        P = self.policy.n_flat
+        self._phase = dict(src=src, S=S, slabs=self._buf("slabs", (ops.mlp_backward_slabs(S), P), zero=True))
+        self._actor_slabs_clean = False
+
+    def phase_update_job(self, epoch):
+        """Epoch `epoch`'s actor + critic update (the arguments of _update_kernels' dual launch) as a job of the grouped launch."""
+        pol, ph = self.policy, self._phase
+        src, S = ph["src"], ph["S"]
+        self._epochs["e"] = epoch
+        vn_state = self._epochs["states"][epoch] if self._use_valuenorm else None       # state after this epoch's ValueNorm.update
+        return ops.update_job(pol.actor.flat, pol.actor.desc, src["obs"], pol.critic.flat, pol.critic.desc, src["share_obs"], None, S,
+                              src["avail"], src["actions"], src["old_logp"], src["adv"], src["active"], src["v_old"], src["returns"],
+                              vn_state, self._mb_moments, self._cfg_acc, ph["slabs"], pol.n_flat, 0, pol.seg_bounds[1], self._pa, self._pc)
+
+    def phase_optim_job(self):
+        """The slab reduction + clip + Adam that follows every epoch's update (the arguments of _update's reduce_clip_adam) as a job."""
+        pol, ph = self.policy, self._phase
+        n_rows = ops.dual_update_slabs(pol.actor.desc, pol.critic.desc, ph["S"])
+        return ops.optim_job(ph["slabs"], n_rows, pol.n_flat, pol.flat_params, pol.flat_grad, pol.exp_avg, pol.exp_avg_sq, pol.seg_bounds,
+                             pol.opt_hyper, pol.opt_step, pol.grad_norms, pol.opt_workspace, norm_acc=self._acc[4:])
+
+    @torch.no_grad()
+    def phase_epilogue(self, buffer, after_update=False):
+        """The statistics launch (with buffer.after_update()'s copies in it when asked for)."""
+        if self._train_epilogue(buffer, self._phase["S"], True, after_update, True):
+            buffer.after_update()
+        self._phase = None
+
+    def phase_info(self):
+        """train()'s return value: the six averaged statistics (the one host sync)."""
+        return self._finish_train_info()
+
+    _phase = None
 
     def compute_advantages(self, buffer):
         """r_mappo.py:174-182 as two kernels around an (optional) 3-double all-reduce."""

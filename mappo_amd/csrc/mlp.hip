@@ -612,6 +612,81 @@ extern "C" int mappo_actor_critic_update(const float *actor_params, const mappo_
   return MAPPO_OK;
 }
 
+// ---- the dual launches of several agents in one (mlp_update16_group_kernel) -----------------------------------------------------
+// Every check comes before the launch and names the job; a job passes exactly when mappo_actor_critic_update would serve it with
+// the 16-sample-tile dual kernel, and its workgroup counts are that call's (upd16_split).
+extern "C" int32_t mappo_update_group_accepts(const mappo_net_desc *actor_desc, const mappo_net_desc *critic_desc) {
+  if (!actor_desc || !critic_desc) return 0;
+  const mappo_net_desc &a = *actor_desc, &c = *critic_desc;
+  return a.hidden == HID && c.hidden == HID && a.in_dim >= 1 && c.in_dim >= 1 && a.out_dim >= 1 && a.layer_N >= 0 && a.layer_N == c.layer_N &&
+         a.use_relu == c.use_relu && (a.use_feature_norm != 0) == (c.use_feature_norm != 0) && upd16_eligible(a, true) && upd16_eligible(c, false);
+}
+
+extern "C" int mappo_actor_critic_update_group(const mappo_update_job *jobs, int32_t n_jobs, mappo_stream_t stream) {
+  const char *who = "actor_critic_update_group";
+  MAPPO_REQUIRE(n_jobs >= 1 && n_jobs <= MAPPO_MAX_GROUP, "%s: n_jobs=%d outside [1,%d] (job count)", who, n_jobs, MAPPO_MAX_GROUP);
+  MAPPO_REQUIRE(jobs, "%s: null job array (job 0)", who);
+  Group16Args g = {};
+  g.n_jobs = n_jobs;
+  const mappo_net_desc &a0 = jobs[0].actor_desc;
+  g.use_feature_norm = a0.use_feature_norm != 0;
+  size_t lds_floats = 0;
+  int blocks = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const mappo_update_job &J = jobs[j];
+    const mappo_net_desc &da = J.actor_desc, &dc = J.critic_desc;
+    MAPPO_REQUIRE(da.hidden == HID && dc.hidden == HID, "%s: job %d: hidden_size %d / %d unsupported (kernels are tiled for %d)", who, j,
+                  da.hidden, dc.hidden, HID);
+    MAPPO_REQUIRE(da.in_dim >= 1 && dc.in_dim >= 1 && da.out_dim >= 1, "%s: job %d: in_dim %d / %d, out_dim %d must be positive", who, j,
+                  da.in_dim, dc.in_dim, da.out_dim);
+    MAPPO_REQUIRE(da.in_dim <= MAXD && dc.in_dim <= MAXD, "%s: job %d: in_dim %d > %d (wide inputs take the single calls)", who, j,
+                  da.in_dim > MAXD ? da.in_dim : dc.in_dim, MAXD);
+    MAPPO_REQUIRE(!da.recurrent && !dc.recurrent, "%s: job %d: recurrent networks are not grouped", who, j);
+    MAPPO_REQUIRE(da.layer_N >= 0 && da.layer_N <= 1 && dc.layer_N == da.layer_N, "%s: job %d: layer_N %d / %d (grouped: 0 or 1, shared by both networks)",
+                  who, j, da.layer_N, dc.layer_N);
+    MAPPO_REQUIRE(da.out_dim <= 16, "%s: job %d: out_dim %d > 16 (a Discrete head of at most 16 actions; MultiDiscrete is not grouped)", who, j, da.out_dim);
+    MAPPO_REQUIRE(dc.out_dim == 1, "%s: job %d: critic out_dim must be 1", who, j);
+    MAPPO_REQUIRE(da.use_relu == dc.use_relu && (da.use_feature_norm != 0) == (dc.use_feature_norm != 0),
+                  "%s: job %d: actor and critic must share the activation and feature normalisation", who, j);
+    MAPPO_REQUIRE(upd16_eligible(da, true) && upd16_eligible(dc, false),
+                  "%s: job %d: an actor with %d inputs and layer_N %d takes the pair kernel (single call only)", who, j, da.in_dim, da.layer_N);
+    MAPPO_REQUIRE(da.layer_N == a0.layer_N, "%s: job %d: layer_N %d differs from job 0's %d (one launch is one kernel instance)", who, j, da.layer_N,
+                  a0.layer_N);
+    MAPPO_REQUIRE((da.use_relu != 0) == (a0.use_relu != 0), "%s: job %d: use_relu %d differs from job 0's %d (one launch is one kernel instance)", who,
+                  j, da.use_relu, a0.use_relu);
+    MAPPO_REQUIRE((da.use_feature_norm != 0) == (a0.use_feature_norm != 0),
+                  "%s: job %d: use_feature_norm %d differs from job 0's %d (one launch is one kernel instance)", who, j, da.use_feature_norm,
+                  a0.use_feature_norm);
+    MAPPO_REQUIRE(J.actor_params && J.critic_params && J.obs && J.share_obs && J.actions && J.old_logp && J.adv && J.active && J.v_old && J.returns &&
+                      J.mb_moments && J.slabs && J.actor_partials && J.critic_partials, "%s: job %d: null pointer", who, j);
+    MAPPO_REQUIRE(J.B > 0, "%s: job %d: B=%lld", who, j, (long long)J.B);
+    MAPPO_REQUIRE(!J.cfg.use_valuenorm || J.vn_state, "%s: job %d: use_valuenorm needs vn_state", who, j);
+    const NetOff oa = net_offsets(da), oc = net_offsets(dc);
+    MAPPO_REQUIRE(J.actor_col0 >= 0 && J.actor_col0 + oa.total <= J.slab_stride && J.critic_col0 >= 0 && J.critic_col0 + oc.total <= J.slab_stride,
+                  "%s: job %d: slab column range", who, j);
+    Group16Job &G = g.job[j];
+    G.actor_params = J.actor_params; G.critic_params = J.critic_params; G.obs = J.obs; G.share_obs = J.share_obs; G.rows = J.rows;
+    G.avail = J.avail; G.actions = J.actions; G.old_logp = J.old_logp; G.adv = J.adv; G.active = J.active; G.v_old = J.v_old;
+    G.returns = J.returns; G.vn_state = J.vn_state; G.mb_moments = J.mb_moments; G.slabs = J.slabs;
+    G.actor_partials = J.actor_partials; G.critic_partials = J.critic_partials;
+    G.B = J.B; G.slab_stride = J.slab_stride; G.actor_col0 = J.actor_col0; G.critic_col0 = J.critic_col0; G.cfg = J.cfg;
+    G.in_a = da.in_dim; G.in_c = dc.in_dim; G.out_a = da.out_dim; G.tot_a = oa.total; G.tot_c = oc.total;
+    G.block0 = blocks;
+    upd16_split(da, dc, J.B, G.nA, G.nC);
+    blocks += G.nA + G.nC;
+    const size_t la = upd16_lds_floats(da, true), lc = upd16_lds_floats(dc, false);
+    lds_floats = la > lds_floats ? la : lds_floats;
+    lds_floats = lc > lds_floats ? lc : lds_floats;
+  }
+  MAPPO_CLEAR_STICKY();
+  const size_t lds_bytes = lds_floats * sizeof(float);      // (<= UPD16_LDS_MAX: upd16_eligible)
+  dim3 grid((unsigned)blocks), block(WAVE * UPD16_WAVES);
+  if (int rc = dispatch_relu_ln<1>(a0.use_relu != 0, a0.layer_N, [&](auto R, auto L) { return upd16g_inst<R.value, L.value>(grid, block, lds_bytes, as_stream(stream), g); }))
+    return rc;
+  MAPPO_CHECK_LAUNCH(who);
+  return MAPPO_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // wide_l1_bwd_kernel: layer-1 weight gradient and feature-norm gradients for in_dim > 64.
 //   dW1[f][k]  = sum_s dz1[f][s] * xn[k][s],   xn = xhat0 * gamma0 + beta0

@@ -10,6 +10,7 @@ struct UpdArgs;
 struct DualArgs;
 struct Upd16Args;
 struct Dual16Args;
+struct Group16Args;
 struct MdHeads;
 struct Wide16Args;
 struct WideBwd16Args;
@@ -67,6 +68,9 @@ template <bool R, int L>
 int upd16md_inst(bool wide, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Upd16Args &a, const MdHeads &md);
 template <bool R, int L>
 int upd16mdd_inst(bool wide_a, bool wide_c, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Dual16Args &d, const MdHeads &md);
+// up to MAPPO_MAX_GROUP dual launches in one (mlp_update16_group_kernel): translation units mlp_upd16g_r{0,1}_l{0,1}.hip
+template <bool R, int L>
+int upd16g_inst(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Group16Args &g);
 // the same network from the layer-1 pre-activations on (in_dim 65..512; layer 1 in mlp_wide16.h / wide_l1_bwd_kernel)
 template <bool R, int L>
 int upd16x_inst(int head, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Upd16Args &a);

@@ -1200,6 +1200,80 @@ __global__ __launch_bounds__(512, 2) void mlp_update16_dual_kernel(Dual16Args d)
   else update16_body<RELU, LN, 2, WIDE_C>(d.c, lds, bid - d.nA, d.nC);
 }
 
+// The dual launches of up to MAPPO_MAX_GROUP (actor, critic) pairs — the agents of a separated run — side by side in ONE launch
+// (mappo_actor_critic_update_group): job j owns workgroups [block0, block0 + nA) for its actor and the nC after them for its
+// critic, the counts its own dual launch would have (upd16_split, mlp.hip).  The table travels in the kernel argument in a
+// compact form (one UpdArgs per network would not fit its 4 KB): what the two networks of a job share is stored once, the
+// descriptor is (in_dim, out_dim) + the launch's common (layer_N, activation: template; feature normalisation), and the flat
+// parameter offsets are recomputed from it on the scalar unit.  A workgroup finds its job with wave-uniform compares, rebuilds
+// the Upd16Args its dual launch would have passed and runs update16_body with its job-local index and count: every slab row,
+// loss-partial row and zero-filled row comes out as the single call writes it.
+struct Group16Job {
+  const float *actor_params, *critic_params, *obs, *share_obs;
+  const int32_t *rows;
+  const float *avail, *actions, *old_logp, *adv, *active, *v_old, *returns, *vn_state;
+  const double *mb_moments;
+  float *slabs;
+  double *actor_partials, *critic_partials;
+  int64_t B, slab_stride, actor_col0, critic_col0;
+  mappo_ppo_cfg cfg;
+  int in_a, in_c, out_a;     // actor / critic in_dim, actor out_dim (critic: 1)
+  int tot_a, tot_c;          // parameter counts (NetOff::total): the column range a network zero-fills for the other one
+  int block0, nA, nC;
+};
+struct Group16Args {
+  Group16Job job[MAPPO_MAX_GROUP];
+  int n_jobs, use_feature_norm;
+};
+static_assert(sizeof(Group16Args) <= 4096, "the job table must fit the kernel argument segment");
+
+template <bool RELU, int LN>
+__device__ __forceinline__ Upd16Args group16_args(const Group16Job &J, bool actor, int fnorm) {
+  Upd16Args a = {};
+  UpdArgs &u = a.u;
+  u.params = actor ? J.actor_params : J.critic_params;
+  u.x = actor ? J.obs : J.share_obs;
+  u.rows = J.rows; u.slabs = J.slabs; u.slab_stride = J.slab_stride; u.slab_col0 = actor ? J.actor_col0 : J.critic_col0;
+  u.desc.in_dim = actor ? J.in_a : J.in_c; u.desc.hidden = HID; u.desc.out_dim = actor ? J.out_a : 1; u.desc.layer_N = LN;
+  u.desc.use_relu = RELU; u.desc.use_feature_norm = fnorm; u.desc.recurrent = 0;
+  u.off = net_offsets(u.desc);
+  u.B = J.B; u.active = J.active; u.mb_moments = J.mb_moments; u.cfg = J.cfg;
+  if (actor) { u.avail = J.avail; u.actions = J.actions; u.old_logp = J.old_logp; u.adv = J.adv; u.partials = J.actor_partials; }
+  else { u.v_old = J.v_old; u.returns = J.returns; u.vn_state = J.vn_state; u.partials = J.critic_partials; }
+  // the network with fewer workgroups: its missing slab / partial rows are zero-filled by the other one's (as in the dual launch)
+  const int mine = actor ? J.nA : J.nC, other = actor ? J.nC : J.nA;
+  if (other < mine) {
+    a.zero_row0 = other; a.zero_row1 = mine;
+    a.zero_col0 = actor ? J.critic_col0 : J.actor_col0; a.zero_cols = actor ? J.tot_c : J.tot_a;
+    a.zero_partials = actor ? J.critic_partials : J.actor_partials;
+  }
+  return a;
+}
+
+template <bool RELU, int LN>
+__global__ __launch_bounds__(512, 2) void mlp_update16_group_kernel(Group16Args g) {
+  extern __shared__ __align__(16) float lds[];
+  const int bid = blockIdx.x;
+  int j = 0;
+#pragma unroll
+  for (int k = 1; k < MAPPO_MAX_GROUP; ++k)
+    if (k < g.n_jobs && bid >= g.job[k].block0) j = k;             // (block0 increases with k; scalar compares)
+  const Group16Job &J = g.job[j];
+  const int bl = bid - J.block0;
+  if (bl < J.nA) {
+    const Upd16Args a = group16_args<RELU, LN>(J, true, g.use_feature_norm);
+    // (an actor with 33..64 inputs and a hidden layer takes the pair kernel: refused on the host, no instance here)
+    if constexpr (LN == 0) {
+      if (J.in_a > 32) { update16_body<RELU, LN, 1, true>(a, lds, bl, J.nA); return; }
+    }
+    update16_body<RELU, LN, 1, false>(a, lds, bl, J.nA);
+  } else {
+    const Upd16Args c = group16_args<RELU, LN>(J, false, g.use_feature_norm);
+    if (J.in_c > 32) update16_body<RELU, LN, 2, true>(c, lds, bl - J.nA, J.nC);
+    else update16_body<RELU, LN, 2, false>(c, lds, bl - J.nA, J.nC);
+  }
+}
+
 // The MultiDiscrete actor (mappo_actor_update_md / mappo_actor_critic_update_md): the same kernels with the multi-head loss
 template <bool RELU, int LN, bool WIDE>
 __global__ __launch_bounds__(512, 2) void mlp_update16_md_kernel(Upd16Args a, MdHeads md) {

@@ -1,12 +1,20 @@
 // mlp_upd16_launch.h — launchers of the 16-sample-tile update kernels (mlp_upd16.h): mlp_update16_kernel, mlp_update16_dual_kernel
-// and mlp_update16x_kernel<MLP_UPD_RELU, MLP_UPD_LN, ...>; included by mlp_upd16_r*_l*.hip, which define the two template parameters.
+// and mlp_update16x_kernel<MLP_UPD_RELU, MLP_UPD_LN, ...>; included by mlp_upd16_r*_l*.hip, which define the two template parameters
+// (mlp_upd16md_r*_l*.hip with MLP_UPD_MD: the MultiDiscrete actor's kernels; mlp_upd16g_r*_l*.hip with MLP_UPD_GROUP: the grouped launch).
 #pragma once
 #include "mlp_upd16.h"
 #include "mlp_launch.h"
 
 static_assert(L16<0, 1, false>::LDS_CAP * 4 == UPD16_LDS_MAX, "L16::LDS_CAP is UPD16_LDS_MAX in floats");
 
-#ifdef MLP_UPD_MD
+#if defined(MLP_UPD_GROUP)
+// several agents' dual launches in one (mlp_update16_group_kernel): translation units mlp_upd16g_r*_l*.hip
+template <bool R, int L>
+int upd16g_inst(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Group16Args &g) {
+  return launch_kernel<mlp_update16_group_kernel<R, L>, UPD16_LDS_MAX, MAPPO_PROF_MLP_BWD>("actor_critic_update_group", grid, block, lds_bytes, st, g);
+}
+template int upd16g_inst<MLP_UPD_RELU, MLP_UPD_LN>(dim3, dim3, size_t, hipStream_t, const Group16Args &);
+#elif defined(MLP_UPD_MD)
 // the MultiDiscrete actor's kernels (mlp_update16_md_kernel, mlp_update16_md_dual_kernel): translation units mlp_upd16md_r*_l*.hip
 template <bool R, int L, bool W>
 static int upd16md_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Upd16Args &a, const MdHeads &md) {

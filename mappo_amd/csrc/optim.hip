@@ -45,10 +45,11 @@ __device__ __forceinline__ float slab_quarter_sum(const float *__restrict__ slab
   return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
 // the workgroup's 128 sums: valid in the threads of quarter 0 (threadIdx.x < 128), 0 elsewhere
-__device__ __forceinline__ float slab_block_sum(const float *__restrict__ slabs, int n_slabs, int64_t stride, int64_t P, int64_t &p_out) {
+__device__ __forceinline__ float slab_block_sum(const float *__restrict__ slabs, int n_slabs, int64_t stride, int64_t P, int64_t &p_out,
+                                                const unsigned bid) {
   __shared__ float sq[SLAB_Q][SLAB_BLOCK];
   const int pi = threadIdx.x & (SLAB_BLOCK - 1), quarter = threadIdx.x / SLAB_BLOCK;
-  const int64_t p = (int64_t)blockIdx.x * SLAB_BLOCK + pi;
+  const int64_t p = (int64_t)bid * SLAB_BLOCK + pi;
   p_out = p;
   sq[quarter][pi] = p < P ? slab_quarter_sum(slabs, n_slabs, stride, p, quarter) : 0.f;
   __syncthreads();
@@ -58,7 +59,7 @@ __device__ __forceinline__ float slab_block_sum(const float *__restrict__ slabs,
 __global__ __launch_bounds__(SLAB_BLOCK * SLAB_Q) void slab_reduce_kernel(const float *__restrict__ slabs, int n_slabs,
                                                                          int64_t stride, int64_t P, float *__restrict__ grad) {
   int64_t p;
-  const float g = slab_block_sum(slabs, n_slabs, stride, P, p);
+  const float g = slab_block_sum(slabs, n_slabs, stride, P, p, blockIdx.x);
   if (threadIdx.x < SLAB_BLOCK && p < P) grad[p] = g;
 }
 
@@ -66,17 +67,23 @@ __global__ __launch_bounds__(SLAB_BLOCK * SLAB_Q) void slab_reduce_kernel(const 
 // kernel here runs a few microseconds, so the launches themselves are what it costs) --------------------------------
 // (1) slab_reduce that also leaves the squared-norm partial of its 128 gradient entries;
 // (2) norm finalisation + Adam in one kernel (see norm_adam_kernel).
-__global__ __launch_bounds__(SLAB_BLOCK * SLAB_Q) void slab_reduce_sq_kernel(const float *__restrict__ slabs, int n_slabs, int64_t stride,
-                                                                            int64_t P, float *__restrict__ grad, double *__restrict__ partials,
-                                                                            const float *__restrict__ hyper, int32_t *step, int n_seg) {
+// (bid: the workgroup's index among those of ITS flat buffer — blockIdx.x, or the job-local index of the grouped launch)
+__device__ __forceinline__ void slab_reduce_sq_body(const float *__restrict__ slabs, int n_slabs, int64_t stride, int64_t P, float *__restrict__ grad,
+                                                    double *__restrict__ partials, const float *__restrict__ hyper, int32_t *step, int n_seg,
+                                                    const unsigned bid) {
   __shared__ double smem[16];
-  if (blockIdx.x == 0 && threadIdx.x < n_seg && hyper[threadIdx.x * 8 + 7] != 0.f) step[threadIdx.x] += 1;   // Adam step of enabled segments
+  if (bid == 0 && threadIdx.x < n_seg && hyper[threadIdx.x * 8 + 7] != 0.f) step[threadIdx.x] += 1;   // Adam step of enabled segments
   int64_t p;
-  const float g = slab_block_sum(slabs, n_slabs, stride, P, p);         // (0 in the threads of quarters 1..3)
+  const float g = slab_block_sum(slabs, n_slabs, stride, P, p, bid);    // (0 in the threads of quarters 1..3)
   if (threadIdx.x < SLAB_BLOCK && p < P) grad[p] = g;
   double v[1] = {(double)g * (double)g};
   block_sum<1>(v, smem);
-  if (threadIdx.x == 0) partials[blockIdx.x] = v[0];
+  if (threadIdx.x == 0) partials[bid] = v[0];
+}
+__global__ __launch_bounds__(SLAB_BLOCK * SLAB_Q) void slab_reduce_sq_kernel(const float *__restrict__ slabs, int n_slabs, int64_t stride,
+                                                                            int64_t P, float *__restrict__ grad, double *__restrict__ partials,
+                                                                            const float *__restrict__ hyper, int32_t *step, int n_seg) {
+  slab_reduce_sq_body(slabs, n_slabs, stride, P, grad, partials, hyper, step, n_seg, blockIdx.x);
 }
 
 // squared-norm partials per 128 gradient entries (+ the Adam step increment of the enabled segments): the first launch of
@@ -96,19 +103,18 @@ __global__ __launch_bounds__(SLAB_BLOCK) void sqnorm128_kernel(const float *__re
 // segment itself (a few dozen partials + two pow()s: redundant across workgroups, but in parallel and without a
 // separate launch), then applies Adam to its slice.  The step counters were advanced by slab_reduce_sq_kernel's first
 // workgroup (a kernel boundary orders that increment before every read here); workgroup 0 also publishes the norms.
-__global__ __launch_bounds__(OPT_BLOCK) void norm_adam_kernel(const double *__restrict__ partials, SegBounds sb,
-                                                             const float *__restrict__ hyper, const int32_t *__restrict__ step,
-                                                             float *__restrict__ grad_norms, double *__restrict__ norm_acc,
-                                                             float *__restrict__ params, const float *__restrict__ grad,
-                                                             float *__restrict__ m, float *__restrict__ v) {
+__device__ __forceinline__ void norm_adam_body(const double *__restrict__ partials, const SegBounds &sb, const float *__restrict__ hyper,
+                                               const int32_t *__restrict__ step, float *__restrict__ grad_norms, double *__restrict__ norm_acc,
+                                               float *__restrict__ params, const float *__restrict__ grad, float *__restrict__ m,
+                                               float *__restrict__ v, const unsigned bid) {
   __shared__ double smem[16];
   __shared__ float ws[4];
-  const int64_t i = (int64_t)blockIdx.x * OPT_BLOCK + threadIdx.x;
-  const int s = seg_of(sb, (int64_t)blockIdx.x * OPT_BLOCK);
+  const int64_t i = (int64_t)bid * OPT_BLOCK + threadIdx.x;
+  const int s = seg_of(sb, (int64_t)bid * OPT_BLOCK);
   const float gi = grad[i], pi = params[i], mi0 = m[i], vi0 = v[i];      // in flight under the norm reduction
-  const int n_seg_pub = (blockIdx.x == 0) ? sb.n : 1;                   // workgroup 0 walks all segments to publish their norms
+  const int n_seg_pub = (bid == 0) ? sb.n : 1;                          // workgroup 0 walks all segments to publish their norms
   for (int k = 0; k < n_seg_pub; ++k) {
-    const int sk = (blockIdx.x == 0) ? (k == 0 ? s : (k <= s ? k - 1 : k)) : s;      // own segment first
+    const int sk = (bid == 0) ? (k == 0 ? s : (k <= s ? k - 1 : k)) : s;             // own segment first
     const int b0 = (int)(sb.b[sk] / SLAB_BLOCK), b1 = (int)(sb.b[sk + 1] / SLAB_BLOCK);
     double acc[1] = {0.0};
     for (int b = b0 + threadIdx.x; b < b1; b += blockDim.x) acc[0] += partials[b];
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(OPT_BLOCK) void norm_adam_kernel(const double *__re
     if (threadIdx.x == 0) {
       const float *h = hyper + sk * 8;
       const float norm = (float)sqrt(acc[0]);
-      if (blockIdx.x == 0) {
+      if (bid == 0) {
         grad_norms[sk] = norm;
         if (norm_acc) norm_acc[sk] += (double)norm;
       }
@@ -146,6 +152,49 @@ __global__ __launch_bounds__(OPT_BLOCK) void norm_adam_kernel(const double *__re
   const float denom = sqrtf(vi) / ws[2] + eps;
   pp = pp - ws[1] * (mi / denom);
   params[i] = pp; m[i] = mi; v[i] = vi;
+}
+__global__ __launch_bounds__(OPT_BLOCK) void norm_adam_kernel(const double *__restrict__ partials, SegBounds sb,
+                                                             const float *__restrict__ hyper, const int32_t *__restrict__ step,
+                                                             float *__restrict__ grad_norms, double *__restrict__ norm_acc,
+                                                             float *__restrict__ params, const float *__restrict__ grad,
+                                                             float *__restrict__ m, float *__restrict__ v) {
+  norm_adam_body(partials, sb, hyper, step, grad_norms, norm_acc, params, grad, m, v, blockIdx.x);
+}
+
+// ---- the same two launches for up to MAPPO_MAX_GROUP flat buffers (mappo_reduce_clip_adam_group: the agents of a separated run).
+// The job table travels in the kernel argument; a workgroup finds its job with wave-uniform compares and runs the single launch's
+// body with its job-local index, so every job's arithmetic and order are the single call's.
+struct OptJob {
+  const float *slabs, *hyper;
+  float *params, *grad, *m, *v, *grad_norms;
+  double *partials, *norm_acc;
+  int32_t *step;
+  int64_t stride;
+  SegBounds sb;
+  int n_slabs;
+  int rblock0, ablock0;      // first workgroup of the job in the reduce launch (P / 128 each) / in the Adam launch (P / 256 each)
+};
+struct OptGroup {
+  OptJob job[MAPPO_MAX_GROUP];
+  int n_jobs;
+};
+static_assert(sizeof(OptGroup) <= 4096, "the job table must fit the kernel argument segment");
+
+__global__ __launch_bounds__(SLAB_BLOCK * SLAB_Q) void slab_reduce_sq_group_kernel(OptGroup g) {
+  int j = 0;
+#pragma unroll
+  for (int k = 1; k < MAPPO_MAX_GROUP; ++k)
+    if (k < g.n_jobs && (int)blockIdx.x >= g.job[k].rblock0) j = k;
+  const OptJob &J = g.job[j];
+  slab_reduce_sq_body(J.slabs, J.n_slabs, J.stride, J.sb.b[J.sb.n], J.grad, J.partials, J.hyper, J.step, J.sb.n, blockIdx.x - (unsigned)J.rblock0);
+}
+__global__ __launch_bounds__(OPT_BLOCK) void norm_adam_group_kernel(OptGroup g) {
+  int j = 0;
+#pragma unroll
+  for (int k = 1; k < MAPPO_MAX_GROUP; ++k)
+    if (k < g.n_jobs && (int)blockIdx.x >= g.job[k].ablock0) j = k;
+  const OptJob &J = g.job[j];
+  norm_adam_body(J.partials, J.sb, J.hyper, J.step, J.grad_norms, J.norm_acc, J.params, J.grad, J.m, J.v, blockIdx.x - (unsigned)J.ablock0);
 }
 
 extern "C" int64_t mappo_optim_workspace_bytes(int64_t P) {
@@ -216,5 +265,41 @@ extern "C" int mappo_reduce_clip_adam(const float *slabs, int32_t n_slabs, int64
   PROF_LAUNCH(MAPPO_PROF_ADAM, norm_adam_kernel, dim3((unsigned)(P / OPT_BLOCK)), dim3(OPT_BLOCK), 0, st, (const double *)partials, sb,
               opt_hyper, (const int32_t *)opt_step, grad_norms, norm_acc, params, (const float *)grad, exp_avg, exp_avg_sq);
   MAPPO_CHECK_LAUNCH("reduce_clip_adam");
+  return MAPPO_OK;
+}
+
+extern "C" int mappo_reduce_clip_adam_group(const mappo_optim_job *jobs, int32_t n_jobs, mappo_stream_t stream) {
+  const char *who = "reduce_clip_adam_group";
+  MAPPO_REQUIRE(n_jobs >= 1 && n_jobs <= MAPPO_MAX_GROUP, "%s: n_jobs=%d outside [1,%d] (job count)", who, n_jobs, MAPPO_MAX_GROUP);
+  MAPPO_REQUIRE(jobs, "%s: null job array (job 0)", who);
+  OptGroup g = {};
+  g.n_jobs = n_jobs;
+  int rblocks = 0, ablocks = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const mappo_optim_job &J = jobs[j];
+    MAPPO_REQUIRE(J.slabs && J.params && J.grad && J.exp_avg && J.exp_avg_sq && J.opt_hyper && J.opt_step && J.grad_norms && J.workspace,
+                  "%s: job %d: null pointer", who, j);
+    MAPPO_REQUIRE(J.n_seg >= 1 && J.n_seg <= OPT_MAX_SEG && J.n_slabs > 0, "%s: job %d: n_seg=%d n_slabs=%d", who, j, J.n_seg, J.n_slabs);
+    OptJob &G = g.job[j];
+    G.sb.n = J.n_seg;
+    for (int s = 0; s <= J.n_seg; ++s) {
+      MAPPO_REQUIRE(J.seg_bounds[s] % OPT_BLOCK == 0 && (s == 0 || J.seg_bounds[s] > J.seg_bounds[s - 1]),
+                    "%s: job %d: segment bounds must be increasing multiples of %d", who, j, OPT_BLOCK);
+      G.sb.b[s] = J.seg_bounds[s];
+    }
+    MAPPO_REQUIRE(J.seg_bounds[0] == 0, "%s: job %d: seg_bounds[0] must be 0", who, j);
+    const int64_t P = J.seg_bounds[J.n_seg];
+    MAPPO_REQUIRE(J.slab_stride >= P, "%s: job %d: slab_stride < P", who, j);
+    G.slabs = J.slabs; G.hyper = J.opt_hyper; G.params = J.params; G.grad = J.grad; G.m = J.exp_avg; G.v = J.exp_avg_sq;
+    G.grad_norms = J.grad_norms; G.partials = (double *)J.workspace; G.norm_acc = J.norm_acc; G.step = J.opt_step;
+    G.stride = J.slab_stride; G.n_slabs = J.n_slabs;
+    G.rblock0 = rblocks; G.ablock0 = ablocks;
+    rblocks += (int)(P / SLAB_BLOCK);                   // P is a multiple of 256: mappo_optim_workspace_bytes(P) covers P/128 doubles
+    ablocks += (int)(P / OPT_BLOCK);
+  }
+  hipStream_t st = as_stream(stream);
+  PROF_LAUNCH(MAPPO_PROF_SLAB_REDUCE, slab_reduce_sq_group_kernel, dim3((unsigned)rblocks), dim3(SLAB_BLOCK * SLAB_Q), 0, st, g);
+  PROF_LAUNCH(MAPPO_PROF_ADAM, norm_adam_group_kernel, dim3((unsigned)ablocks), dim3(OPT_BLOCK), 0, st, g);
+  MAPPO_CHECK_LAUNCH(who);
   return MAPPO_OK;
 }

@@ -600,6 +600,37 @@ def actor_critic_update(actor_params, actor_desc, obs, critic_params, critic_des
     _lib.check(rc, "mappo_actor_critic_update")
 
 
+def update_job(actor_params, actor_desc, obs, critic_params, critic_desc, share_obs, rows, B, avail, actions, old_logp, adv, active, v_old,
+               returns, vn_state, mb_moments, cfg, slabs, slab_stride, actor_col0, critic_col0, actor_partials, critic_partials):
+    """The arguments of actor_critic_update as one job of actor_critic_update_group (the tensors must outlive the launch)."""
+    v = lambda p: p.value if p is not None else None
+    o = lambda t: v(_ptr(t, allow_none=True))
+    j = _lib.UpdateJob()
+    j.actor_params, j.obs, j.critic_params, j.share_obs = v(_ptr(actor_params)), v(_ptr(obs)), v(_ptr(critic_params)), v(_ptr(share_obs))
+    C.memmove(C.byref(j.actor_desc), C.byref(actor_desc), C.sizeof(NetDesc))
+    C.memmove(C.byref(j.critic_desc), C.byref(critic_desc), C.sizeof(NetDesc))
+    C.memmove(C.byref(j.cfg), C.byref(cfg), C.sizeof(PpoCfg))
+    j.rows, j.B, j.avail = v(_ptr(rows, torch.int32, allow_none=True)), int(B), o(avail)
+    j.actions, j.old_logp, j.adv, j.active = v(_ptr(actions)), v(_ptr(old_logp)), v(_ptr(adv)), v(_ptr(active))
+    j.v_old, j.returns, j.vn_state, j.mb_moments = v(_ptr(v_old)), v(_ptr(returns)), o(vn_state), v(_ptr(mb_moments, torch.float64))
+    j.slabs, j.slab_stride, j.actor_col0, j.critic_col0 = v(_ptr(slabs)), int(slab_stride), int(actor_col0), int(critic_col0)
+    j.actor_partials, j.critic_partials = v(_ptr(actor_partials, torch.float64)), v(_ptr(critic_partials, torch.float64))
+    return j
+
+
+def update_group_accepts(actor_desc, critic_desc):
+    """Whether actor_critic_update_group takes a job of these two networks (host-only: no device needed)."""
+    return bool(_lib.load().mappo_update_group_accepts(C.byref(actor_desc), C.byref(critic_desc)))
+
+
+def actor_critic_update_group(jobs):
+    """len(jobs) (1..8) actor_critic_update calls in ONE launch (mappo_actor_critic_update_group): every job's slab rows and loss
+    partials are bit for bit the single call's.  Narrow feed-forward Discrete jobs of one (layer_N, activation, feature norm) only."""
+    arr = (_lib.UpdateJob * len(jobs))(*jobs) if jobs else None
+    rc = _lib.load().mappo_actor_critic_update_group(arr, len(jobs), _stream())
+    _lib.check(rc, "mappo_actor_critic_update_group")
+
+
 def update_stats(actor_partials, n_actor, critic_partials, n_critic, mb_moments, cfg, stats, acc=None):
     rc = _lib.load().mappo_update_stats(_ptr(actor_partials, torch.float64, allow_none=True), int(n_actor),
                                         _ptr(critic_partials, torch.float64), int(n_critic), _ptr(mb_moments, torch.float64),
@@ -781,6 +812,31 @@ def reduce_clip_adam(slabs, n_slabs, slab_stride, params, grad, exp_avg, exp_avg
                                             _ptr(exp_avg_sq), arr, n_seg, _ptr(opt_hyper), _ptr(opt_step, torch.int32), _ptr(grad_norms),
                                             _ptr(norm_acc, torch.float64, allow_none=True), _ptr(workspace, torch.uint8), _stream())
     _lib.check(rc, "mappo_reduce_clip_adam")
+
+
+def optim_job(slabs, n_slabs, slab_stride, params, grad, exp_avg, exp_avg_sq, seg_bounds, opt_hyper, opt_step, grad_norms, workspace,
+              norm_acc=None):
+    """The arguments of reduce_clip_adam as one job of reduce_clip_adam_group."""
+    v = lambda p: p.value if p is not None else None
+    j = _lib.OptimJob()
+    j.slabs, j.n_slabs, j.slab_stride = v(_ptr(slabs)), int(n_slabs), int(slab_stride)
+    j.params, j.grad, j.exp_avg, j.exp_avg_sq = v(_ptr(params)), v(_ptr(grad)), v(_ptr(exp_avg)), v(_ptr(exp_avg_sq))
+    n_seg = len(seg_bounds) - 1
+    if not 1 <= n_seg <= 4:
+        raise ValueError(f"optim_job: {n_seg} segments (1..4)")
+    for s, b in enumerate(seg_bounds):
+        j.seg_bounds[s] = int(b)
+    j.n_seg = n_seg
+    j.opt_hyper, j.opt_step, j.grad_norms = v(_ptr(opt_hyper)), v(_ptr(opt_step, torch.int32)), v(_ptr(grad_norms))
+    j.norm_acc, j.workspace = v(_ptr(norm_acc, torch.float64, allow_none=True)), v(_ptr(workspace, torch.uint8))
+    return j
+
+
+def reduce_clip_adam_group(jobs):
+    """len(jobs) (1..8) reduce_clip_adam calls in the same two launches (mappo_reduce_clip_adam_group), bit-identical per job."""
+    arr = (_lib.OptimJob * len(jobs))(*jobs) if jobs else None
+    rc = _lib.load().mappo_reduce_clip_adam_group(arr, len(jobs), _stream())
+    _lib.check(rc, "mappo_reduce_clip_adam_group")
 
 
 def selftest_mfma(A, Bm, D):

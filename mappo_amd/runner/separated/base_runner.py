@@ -2,9 +2,15 @@
 and SeparatedReplayBuffer PER AGENT (lists indexed by agent id), all on the HIP kernels of the shared path.  Every agent's
 networks live in their own flat parameter buffer; `compute` / `train` run the agents one after the other (the same
 launches as the shared runner with M = 1).  The ROLLOUT of agents with feed-forward policies on the GPU-resident
-simple_speaker_listener and simple_adversary envs is batched into one launch (separated/mpe_runner.py,
-mappo_rollout_episode_comm / mappo_rollout_episode_adversary); batching the agents'
-PPO updates is the next step."""
+MPE envs is batched into one launch (separated/mpe_runner.py, mappo_rollout_episode_*).
+
+With MAPPO_SEPARATED_GROUP_TRAIN=1 `train` batches the agents' PPO updates as well: per epoch one update launch
+(mappo_actor_critic_update_group) and one optimiser call (mappo_reduce_clip_adam_group, two launches) for up to 8 agents,
+between per-agent prologues and epilogues, the whole sequence in one hipGraph — bit for bit what the sequential path
+computes.  It applies when EVERY agent's trainer qualifies (R_MAPPO.phase_ready: fused dual update on the 16-sample-tile
+kernel — both networks feed-forward with at most 64 inputs, Discrete head of at most 16 actions, layer_N <= 1 — whole-buffer
+minibatch, single process); otherwise, and without the flag, all agents train sequentially as before (simple_world_comm with
+its 192-wide critics and MultiDiscrete leader, rmappo, num_mini_batch > 1).  Measurements: DESIGN.md §5."""
 import os
 
 import torch
@@ -55,12 +61,78 @@ class Runner(_SharedRunner):
 
     # separated/base_runner.py:120-129
     def train(self):
+        if self._group_train_ready():
+            return self._train_grouped()
         train_infos = []
         for agent_id in range(self.num_agents):
             self.trainer[agent_id].prep_training()
             train_infos.append(self.trainer[agent_id].train(self.buffer[agent_id]))
             self.buffer[agent_id].after_update()
         return train_infos
+
+    # ---- MAPPO_SEPARATED_GROUP_TRAIN=1: the agents' PPO updates side by side -------------------------------------------------
+    GROUP_FLAG = "MAPPO_SEPARATED_GROUP_TRAIN"
+    GROUP_MAX = 8                      # agents per grouped launch (MAPPO_MAX_GROUP); more agents split into groups of at most this many
+    _group_graphs = None
+    _group_warned = False
+
+    def _group_train_ready(self):
+        """Opt-in, and all or nothing: one agent whose trainer does not qualify (R_MAPPO.phase_ready: recurrent, wide critic,
+        MultiDiscrete, num_mini_batch > 1, ...) or that disagrees with the others in (layer_N, activation, feature normalisation)
+        keeps the whole run on the sequential path above, with one warning."""
+        if os.environ.get(self.GROUP_FLAG, "0") == "0":
+            return False
+        d0 = self.policy[0].actor.desc
+        same = lambda d: (d.layer_N, d.use_relu, d.use_feature_norm) == (d0.layer_N, d0.use_relu, d0.use_feature_norm)
+        bad = [m for m, tr in enumerate(self.trainer) if not (tr.phase_ready() and same(tr.policy.actor.desc))]
+        if bad and not self._group_warned:
+            import warnings
+            warnings.warn(f"{self.GROUP_FLAG}: agent(s) {bad} do not qualify for the grouped PPO update; every agent trains sequentially")
+            self._group_warned = True
+        return not bad
+
+    def _train_grouped(self):
+        """Per-agent prologues, per epoch ONE update launch and ONE optimiser call (two launches) per group of at most 8 agents,
+        per-agent epilogues with after_update's copies inside: the launches a sequential train() makes per agent, bit for bit,
+        2 A + 3 E ceil(A / 8) + A of them instead of A (3 + 3 E) + A.  Captured into one hipGraph after a warm eager pass, like
+        R_MAPPO.train."""
+        from mappo_amd import ops
+        trs, bufs = self.trainer, self.buffer
+        G = min(int(self.GROUP_MAX), ops._lib.MAX_GROUP)
+        groups = [range(i, min(i + G, len(trs))) for i in range(0, len(trs), G)]
+
+        def body():
+            for tr, b in zip(trs, bufs):
+                tr.phase_prologue(b)
+            for epoch in range(trs[0].ppo_epoch):
+                for g in groups:
+                    ops.actor_critic_update_group([trs[m].phase_update_job(epoch) for m in g])
+                    ops.reduce_clip_adam_group([trs[m].phase_optim_job() for m in g])
+            for tr, b in zip(trs, bufs):
+                tr.phase_epilogue(b, after_update=True)
+
+        for tr in trs:
+            tr.prep_training()
+            tr.phase_sync()
+        if not all(tr._use_graph for tr in trs):
+            body()
+        else:
+            if self._group_graphs is None:
+                self._group_graphs = {}
+            key = tuple(id(b) for b in bufs)                  # (the runner holds its buffers: the ids cannot be reused)
+            state = self._group_graphs.get(key)
+            if state is None:
+                body()                                        # eager: allocates workspaces
+                self._group_graphs[key] = "warm"
+            else:
+                if state == "warm":
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        body()
+                    self._group_graphs[key] = state = g
+                state.replay()
+        return [tr.phase_info() for tr in trs]
 
     # separated/base_runner.py:131-146: actor_agent{i}.pt / critic_agent{i}.pt (+ vnorm_agent{i}.pt as the shared runner adds)
     def save(self):
