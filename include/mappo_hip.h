@@ -548,6 +548,24 @@ int mappo_rollout_episode_spread(const float *actor_params, const mappo_net_desc
                                  uint64_t counter, const uint64_t *counter_dev, float *obs_buf, float *share_buf, float *rew_buf,
                                  float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/, float *values /*[T][B]*/,
                                  float *next_values /*[B]*/, int32_t centralized, mappo_stream_t stream);
+/* The same episode for a RECURRENT shared policy (csrc/rollout_spread_rec.h): what T x (mappo_recurrent_step_dual +
+ * mappo_mpe_spread_step with action_mode 1 + mappo_insert_mpe_rnn) do, bit for bit while the stepwise step is the fused one
+ * (N*M <= 1024 rows).  Per step t < T: actor and critic (trunk, GRU step on rnn_states[t] * mask_buf[t], rnn.norm, head) on the rows
+ * of step t (step 0: slot 0 of obs_buf / share_buf / rnn_states / rnn_states_critic / mask_buf) -> actions / logp / values [T][B],
+ * sampling with counter + t (+ *counter_dev) and the row index; the environments step as above; obs / share / 1 - done -> slot t + 1,
+ * rewards -> slot t, next states * (1 - done) -> rnn_states / rnn_states_critic [T+1][B][64] slot t + 1.  The bootstrap value of
+ * slot T is NOT computed (the caller takes it through mappo_mlp_features + mappo_gru_forward, as the stepwise path does).
+ * Limits, each refused with a message that names it: both descriptors recurrent; both in_dim <= 64; layer_N <= 1; same layer_N and
+ * activation; actor out_dim 5 and in_dim = 4 + 2L + 4(M-1); critic out_dim 1 and in_dim = M * in_dim (centralized) or in_dim;
+ * M, L in 1..8; no available actions.  Validates on the host before the launch. */
+int mappo_rollout_episode_spread_recurrent(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *critic_params,
+                                           const mappo_net_desc *critic_desc /*host*/, int32_t T, int32_t N, int32_t M, int32_t L,
+                                           int32_t env_episode_length, uint64_t env_seed, double *agent_pos, double *agent_vel,
+                                           double *landmark_pos, int32_t *tstep, int64_t *episode, int32_t deterministic, uint64_t seed,
+                                           uint64_t counter, const uint64_t *counter_dev, float *obs_buf, float *share_buf, float *rew_buf,
+                                           float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/, float *values /*[T][B]*/,
+                                           float *rnn_states /*[T+1][B][64]*/, float *rnn_states_critic /*[T+1][B][64]*/,
+                                           int32_t centralized, mappo_stream_t stream);
 
 /* GPU-vectorised MPE simple_reference (csrc/mpe_ref_env.hip, device functions in csrc/mpe_ref_core.h): N environments of
  * the scenario's fixed shape — 2 agents, 3 landmarks, dim_c = 10, action space MultiDiscrete([[0, 4], [0, 9]]) — one launch per step.

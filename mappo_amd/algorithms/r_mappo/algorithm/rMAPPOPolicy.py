@@ -246,6 +246,39 @@ class R_MAPPOPolicy:
                                    b.actions, b.action_log_probs, b.value_preds, next_values, centralized)
         return next_values
 
+    def can_fuse_episode_recurrent(self):
+        """mappo_rollout_episode_spread_recurrent: both networks recurrent with recurrent_N = 1, narrow inputs (<= 64), layer_N <= 1,
+        the same trunk shape, one Categorical head."""
+        from mappo_amd import recurrent
+        if not (getattr(self.actor, "_recurrent", False) and getattr(self.critic, "_recurrent", False)):
+            return False
+        a, c = self.actor.desc, self.critic.desc
+        return (recurrent.can_step_dual(self.actor, self.critic) and max(a.in_dim, c.in_dim) <= 64 and a.layer_N <= 1
+                and not self.actor.head_dims)
+
+    @torch.no_grad()
+    def collect_episode_env_fused_recurrent(self, buffer, env_state, centralized=True, deterministic=False):
+        """A whole rollout episode of a recurrent policy on the GPU-resident simple_spread env in one launch, env steps included
+        (mappo_rollout_episode_spread_recurrent): `env_state` = SimpleSpreadVecEnv.episode_state().  Writes what T x (collect_into +
+        env.step + insert) write — buffer.{actions, action_log_probs, value_preds, rewards}[0..T-1], obs / share_obs / masks /
+        rnn_states / rnn_states_critic [1..T] — and leaves the env's state where T steps leave it.  The bootstrap value is the
+        caller's (compute()).  Step t samples with counter t + *_counter_dev, as the stepwise path does."""
+        b, st = buffer, env_state
+        T, N, M = b.episode_length, b.n_rollout_threads, b.num_agents
+        if (st["N"], st["M"]) != (N, M) or st["agent_pos"].device != self.device:
+            raise ValueError("collect_episode_env_fused_recurrent: the env does not match the buffer (threads / agents / device)")
+        if not all(t.is_contiguous() for t in (b.obs, b.share_obs, b.rewards, b.masks, b.actions, b.action_log_probs, b.value_preds,
+                                               b.rnn_states, b.rnn_states_critic)):
+            raise ValueError("collect_episode_env_fused_recurrent: the buffer does not have the device layout "
+                             "mappo_rollout_episode_spread_recurrent writes")
+        if b.recurrent_N != 1 or b.rnn_states.shape[-1] != 64:
+            raise ValueError("collect_episode_env_fused_recurrent: needs recurrent_N = 1 and hidden_size 64")
+        ops.rollout_episode_spread_recurrent(self.actor.flat, self.actor.desc, self.critic.flat, self.critic.desc, T, N, M, st["L"], st["T"],
+                                             st["seed"], st["agent_pos"], st["agent_vel"], st["landmark_pos"], st["tstep"], st["episode"],
+                                             deterministic, self.actor._seed, 0, self.actor._counter_dev, b.obs, b.share_obs, b.rewards,
+                                             b.masks, b.actions, b.action_log_probs, b.value_preds, b.rnn_states, b.rnn_states_critic,
+                                             centralized)
+
     def can_fuse_episode_reference(self):
         """mappo_rollout_episode_reference: the MultiDiscrete (5, 10) policy of MPE simple_reference — 21 observation features, a
         critic on 42 (centralized) or 21, what the stepwise MultiDiscrete launch covers (narrow, layer_N <= 1, not recurrent)."""

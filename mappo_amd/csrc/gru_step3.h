@@ -134,25 +134,38 @@ __device__ __forceinline__ void gru_step3_load(Step3W<TLN> &W, const GruFwdArgs 
 
 // TR 3: the tile's trunk features arrive through LDS, xs[b][lane] = features 16 b + 4 q .. + 3 of row n (written by the wave that
 // ran the trunk of a wide-input network in the same workgroup, behind a barrier: mlp_wide16.h, wide_recurrent_step_dual_kernel)
-template <int HM, int TR, int TLN>
+// TR 4 | 5: one step of the one-launch recurrent episode (rollout_spread_rec.h; fused ReLU | tanh trunk with its weights in LDS).
+// The workgroup holds TWO networks of four waves each, which come through here side by side (every barrier below is passed by
+// both; each has its own Step3Shared); `ep` (Step3Ep) names the tile: input rows, previous state and masks in LDS, buffer rows
+// ep->row0 .. + ep->R - 1 of slot offset ep->so, sampling counter ep->ctr.  The new state goes to the next step's LDS tile and
+// stays in *h_keep for the caller, which stores it once the env step has said whether the row's episode ended.
+struct Step3NoEp {};
+template <int HM, int TR, int TLN, class EP = Step3NoEp>
 __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruFwdArgs &p, Step3Shared &sh, const int bid, const int nb,
-                                                const float4 *xs = nullptr) {
-  const int lane = threadIdx.x & (WAVE - 1), w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), n = lane & 15, q = lane >> 4;
-  const int n_tiles = (p.Nc + 15) / 16;
+                                                const float4 *xs = nullptr, const EP *ep = nullptr, g4_t *h_keep = nullptr) {
+  const int lane = threadIdx.x & (WAVE - 1), n = lane & 15, q = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)) & (TR >= 4 ? 3 : ~0);
+  const int n_tiles = TR >= 4 ? 1 : (p.Nc + 15) / 16;
+  int64_t so = 0;                                               // slot offset of the outputs (TR >= 4: step t of the episode)
+  if constexpr (TR >= 4) so = ep->so;
   const int64_t B = p.Nc;                                       // L == 1: column = sequence
   const int A = p.A;
+  if constexpr (TR >= 4) __builtin_assume(A <= 16);             // (the episode's entry point takes 5 actions: no second head block)
   const int u0 = 16 * w + 4 * q;
   const g4_t (&wi)[3][4] = W.wi, (&wh)[3][4] = W.wh;
   const Trunk16R<TLN> &tw = W.tw;
   const g4_t bir = W.bir, biz = W.biz, bin = W.bin, bhr = W.bhr, bhz = W.bhz, bhn = W.bhn, nw4 = W.nw4, nb4 = W.nb4;
   const g4_t hw[2] = {W.hw[0], W.hw[1]};
   for (int tile = bid; tile < n_tiles; tile += nb) {
-    const int c = tile * 16 + n;
-    const bool ok = c < p.Nc;
+    int c = tile * 16 + n;
+    bool ok = c < p.Nc;
+    if constexpr (TR >= 4) { c = ep->row0 + n; ok = n < ep->R; }
     const int cc = ok ? c : 0;
-    const int64_t hrow = p.h0_rows ? (int64_t)p.h0_rows[cc] : (int64_t)cc;
+    const int64_t hrow = (TR < 4 && p.h0_rows) ? (int64_t)p.h0_rows[cc] : (int64_t)cc;
     float mk;
-    if (p.dones) {
+    if constexpr (TR >= 4) {
+      mk = ok ? ep->mk[n] : 0.f;
+    } else if (p.dones) {
       const int env = cc / p.done_M;
       bool all = true;
       for (int m = 0; m < p.done_M; ++m) all = all && p.dones[env * p.done_sn + m * p.done_sm] != 0;
@@ -170,6 +183,17 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
         x[b][0] = t.x; x[b][1] = t.y; x[b][2] = t.z; x[b][3] = t.w;
         hm[b] = g4_load(p.h0 + hrow * HID + 16 * b + 4 * q);
       }
+    } else if constexpr (TR >= 4) {
+      const int D = p.desc.in_dim;
+      f32x4 xin[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xin[b][i] = ep->xrow[min(16 * b + 4 * q + i, D - 1)];
+      trunk16r_apply<TR == 4, TLN>(ep->tw, xin, x, D, ok, p.desc.use_feature_norm != 0, q);
+      ep->late();                                               // a wave whose GRU slices (W.wi / W.wh) wait in LDS takes them now
+#pragma unroll
+      for (int b = 0; b < 4; ++b) hm[b] = *reinterpret_cast<const g4_t *>(ep->hs + n * ep->hs_stride + 16 * b + 4 * q);
     } else if constexpr (TR != 0) {
       const int D = p.desc.in_dim;
       const float *xr = p.x_rows + (int64_t)cc * D;
@@ -215,7 +239,10 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
       const float gn = tanhf_(ain[i] + gr * ahn[i]);
       h[i] = (1.f - gz) * gn + gz * hprev[i];
     }
-    if (p.h_last && ok) {
+    if constexpr (TR >= 4) {
+      *reinterpret_cast<g4_t *>(ep->hs_next + n * ep->hs_stride + u0) = h;
+      *h_keep = h;
+    } else if (p.h_last && ok) {
       g4u_t o; o[0] = h[0]; o[1] = h[1]; o[2] = h[2]; o[3] = h[3];
       *reinterpret_cast<g4u_t *>(p.h_last + (int64_t)c * HID + u0) = o;
     }
@@ -256,7 +283,7 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
           const int a = 16 * bo + 4 * q + i;
           if (a < A) {
             const float v = z[bo][i] + p.params[p.off.bh + a];
-            if (HM == 1) { if (ok) p.out[(int64_t)c * A + a] = v; }
+            if (HM == 1) { if (ok) p.out[(so + c) * A + a] = v; }
             else sh.tZ[n][a] = v;
           }
         }
@@ -264,11 +291,13 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
       if (HM == 2) {
         wave_lds_sync();
         if (q == 0 && ok) {
-          const uint64_t ctr = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);
+          uint64_t ctr;
+          if constexpr (TR >= 4) ctr = ep->ctr; else ctr = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);
           float action, logp;
           categorical_act_mask(&sh.tZ[n][0], A, dead, p.deterministic != 0, p.seed, ctr, (uint64_t)c, action, logp);
-          p.actions[c] = action;
-          p.logp[c] = logp;
+          p.actions[so + c] = action;
+          p.logp[so + c] = logp;
+          if constexpr (TR >= 4) ep->act[n] = action;
         }
       }
     }

@@ -368,6 +368,24 @@ def rollout_episode_spread(actor_params, actor_desc, critic_params, critic_desc,
     _lib.check(rc, "mappo_rollout_episode_spread")
 
 
+def rollout_episode_spread_recurrent(actor_params, actor_desc, critic_params, critic_desc, T, N, M, L, env_episode_length, env_seed,
+                                     agent_pos, agent_vel, landmark_pos, tstep, episode, deterministic, seed, counter, counter_dev,
+                                     obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values, rnn_states, rnn_states_critic,
+                                     centralized):
+    """The one-launch simple_spread episode of a recurrent shared policy (mappo_rollout_episode_spread_recurrent): as
+    rollout_episode_spread, with the buffer's two rnn-state arrays [T+1, N, M, 1, 64] read at slot 0 and written at slots 1..T,
+    and without the bootstrap value."""
+    f64 = torch.float64
+    rc = _lib.load().mappo_rollout_episode_spread_recurrent(
+        _ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), int(T), int(N), int(M), int(L),
+        int(env_episode_length), int(env_seed) & (2 ** 64 - 1), _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
+        _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(bool(deterministic)), int(seed) & (2 ** 64 - 1),
+        int(counter) & (2 ** 64 - 1), _ptr(counter_dev, torch.int64, allow_none=True), _ptr(obs_buf), _ptr(share_buf), _ptr(rew_buf),
+        _ptr(mask_buf), _ptr(actions), _ptr(logp), _ptr(values), _ptr(rnn_states), _ptr(rnn_states_critic), int(bool(centralized)),
+        _stream())
+    _lib.check(rc, "mappo_rollout_episode_spread_recurrent")
+
+
 def rollout_episode_reference(actor_params, actor_desc, critic_params, critic_desc, head_dims, T, N, env_episode_length, env_seed,
                               agent_pos, agent_vel, landmark_pos, goal, tstep, episode, deterministic, seed, counter, counter_dev, obs_buf,
                               share_buf, rew_buf, mask_buf, actions, logp, values, next_values, centralized):

@@ -5,6 +5,7 @@ The rollout step is fused: `collect` runs the actor (sampling + log-prob) and cr
 (R_MAPPOPolicy.collect_into); `insert` only stores what the environment produced.  Nothing crosses PCIe when
 the vec-env yields device tensors (mappo_amd.envs.synthetic); NumPy-returning envs (the reference's
 Dummy/SubprocVecEnv) work too — their arrays are uploaded by the buffer."""
+import os
 import time
 
 import numpy as np
@@ -114,6 +115,16 @@ class MPERunner(Runner):
             b.step = 0
             self.trainer.prep_rollout()
             b.compute_returns(nv, self.trainer.value_normalizer)
+            return infos
+        if (os.environ.get("MAPPO_SPREAD_REC_EPISODE", "0") == "1" and self._episode_state_env()
+                and self.trainer.policy.can_fuse_episode_recurrent()):
+            # opt-in: a recurrent policy on the device-resident simple_spread env — steps 0 .. T-1 (both networks' GRU steps, env
+            # steps, every buffer write) are ONE launch (mappo_rollout_episode_spread_recurrent), same buffer contents and env state
+            # as the stepwise loop below; the bootstrap value stays compute()'s
+            self.trainer.prep_rollout()
+            self.trainer.policy.collect_episode_env_fused_recurrent(self.buffer, self.envs.episode_state(), self.use_centralized_V)
+            self.buffer.step = 0
+            self.compute()
             return infos
         pending = None                     # env output of the previous step, not yet in the buffer (fused path)
         for step in range(self.episode_length):
