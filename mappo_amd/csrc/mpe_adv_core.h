@@ -1,7 +1,16 @@
 // mpe_adv_core.h — the MPE `simple_adversary` ("physical deception") environment as device functions: reset, one environment step
-// and the observation write, one lane per environment.  Shared by the stepwise kernels (mpe_adv_env.hip) and the one-launch rollout
-// episode (rollout_adversary.h), so a step computes the same float64 values whichever launch runs it.  Reference sites: see
-// mpe_adv_env.hip.
+// and the observation write, one lane per environment, and the traits (MpeAdv, at the end) through which the shared kernels reach
+// them: the stepwise kernels (mpe_ragged_env.h) and the one-launch rollout episode (rollout_sep_img.h), so a step computes the same
+// float64 values whichever launch runs it.
+//
+// Reference: onpolicy/envs/mpe/environment.py:194-256 (action decoding), :49-50,142 (world.collaborative is not set: per-agent
+// rewards), :179-185 (time-limit done); onpolicy/envs/mpe/core.py:207-287 (World.step: action force, damping + integration; nothing
+// collides); onpolicy/envs/mpe/scenarios/simple_adversary.py:36-53 (reset), :74-116 (reward), :119-137 (observation); and the
+// reset-on-done of the vec-env wrappers (envs/env_wrappers.py:146-152).
+//
+// Float64 as in the reference's NumPy code; the only function beyond add and multiply is a correctly rounded sqrt, and with
+// contraction off the outputs EQUAL the fp32 cast of the reference's (tests/golden/mpe_adversary.npz).  State is device resident;
+// resets draw from the counter-based Philox stream keyed by (seed, episode, index) — index layout below.
 //
 // Fixed shape (num_agents = 3: one adversary, num_agents - 1 good agents and as many landmarks): agent 0 is the ADVERSARY (observes
 // the two landmarks and the two others relative to itself: 8 features; it is not told which landmark is the goal), agents 1 and 2
@@ -24,10 +33,6 @@
 #define MPE_ADV_OBS_G 10                                            // good agent: 2 + 2 L + 2 (M - 1)
 #define MPE_ADV_SHARE (MPE_ADV_OBS_A + 2 * MPE_ADV_OBS_G)           // the three observations side by side, adversary first
 #define MPE_ADV_DRAWS 16
-
-// where agent m's observation starts in the share row, and its width
-__host__ __device__ constexpr int mpe_adv_obs_off(int m) { return m == 0 ? 0 : MPE_ADV_OBS_A + (m - 1) * MPE_ADV_OBS_G; }
-__host__ __device__ constexpr int mpe_adv_obs_dim(int m) { return m == 0 ? MPE_ADV_OBS_A : MPE_ADV_OBS_G; }
 
 struct MpeAdvArgs {
   double *apos, *avel, *lpos;      // agents [N][3][2], [N][3][2]; landmarks [N][2][2]
@@ -177,3 +182,21 @@ __device__ __forceinline__ bool mpe_adv_step_env(const MpeAdvArgs &a, int n, con
   mpe_adv_write_obs(o0, o1, o2, s);
   return done;
 }
+
+// What the shared kernels need of the scenario, in the one form they take it in.  obs_off / obs_dim: where agent m's observation
+// starts in the share row, and its width.
+struct MpeAdv {
+  typedef MpeAdvArgs Args;
+  typedef MpeAdvState State;
+  static constexpr int M = MPE_ADV_M, U = MPE_ADV_U, SHARE = MPE_ADV_SHARE;
+  __host__ __device__ static constexpr int obs_dim(int m) { return m == 0 ? MPE_ADV_OBS_A : MPE_ADV_OBS_G; }
+  __host__ __device__ static constexpr int obs_off(int m) { return m == 0 ? 0 : MPE_ADV_OBS_A + (m - 1) * MPE_ADV_OBS_G; }
+  static __device__ __forceinline__ void load(const Args &a, int n, State &s) { mpe_adv_load(a, n, s); }
+  static __device__ __forceinline__ void store(const Args &a, int n, const State &s, bool landmarks) { mpe_adv_store(a, n, s, landmarks); }
+  static __device__ __forceinline__ void reset_env(const Args &a, int n, State &s, int64_t ep) { mpe_adv_reset_env(a, n, s, ep); }
+  static __device__ __forceinline__ void write_obs(float *const (&o)[M], const State &s) { mpe_adv_write_obs(o[0], o[1], o[2], s); }
+  static __device__ __forceinline__ bool step_env(const Args &a, int n, const float *act, int act_stride, State &s, float *const (&o)[M],
+                                                  float (&reward)[M]) {
+    return mpe_adv_step_env(a, n, act, act_stride, s, o[0], o[1], o[2], reward);
+  }
+};

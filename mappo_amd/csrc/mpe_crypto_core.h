@@ -1,6 +1,17 @@
 // mpe_crypto_core.h — the MPE `simple_crypto` environment as device functions: reset, one environment step and the observation
-// write, one lane per environment.  Shared by the stepwise kernels (mpe_crypto_env.hip) and the one-launch rollout episode
-// (rollout_crypto.h), so a step computes the same values whichever launch runs it.  Reference sites: see mpe_crypto_env.hip.
+// write, one lane per environment, and the traits (MpeCrypto, at the end) through which the shared kernels reach them: the stepwise
+// kernels (mpe_ragged_env.h) and the one-launch rollout episode (rollout_sep_img.h), so a step computes the same values whichever
+// launch runs it.
+//
+// Reference: onpolicy/envs/mpe/environment.py:194-256 (action decoding: an agent that does not move and is not silent speaks its whole
+// action vector), :49-50,142 (world.collaborative is not set: per-agent rewards), :179-185 (time-limit done);
+// onpolicy/envs/mpe/core.py:280-287 (state.c = action.c, no noise); onpolicy/envs/mpe/scenarios/simple_crypto.py:21-44 (nobody moves
+// or collides, dim_c 4), :47-75 (reset), :94-121 (reward), :124-171 (observation); and the reset-on-done of the vec-env wrappers
+// (envs/env_wrappers.py:146-152).
+//
+// There is no arithmetic to round: every observation is a one-hot or zeros and every reward is -2, 0 or 2, so the outputs EQUAL the
+// fp32 cast of the reference's (tests/golden/mpe_crypto.npz).  State is device resident; resets draw from the counter-based Philox
+// stream keyed by (seed, episode, index) — index layout below.
 //
 // Fixed shape (num_agents = 3, num_landmarks L = 2, 3 or 4): agent 0 is the ADVERSARY "Eve" (a listener: observes what the speaker
 // said, 4 features), agent 1 the good listener "Bob" (the key, then what the speaker said: 8 features), agent 2 the SPEAKER "Alice"
@@ -26,10 +37,6 @@
 #define MPE_CRYPTO_SHARE (MPE_CRYPTO_OBS_E + MPE_CRYPTO_OBS_B + MPE_CRYPTO_OBS_A)    // the three side by side, Eve first: 20
 #define MPE_CRYPTO_DRAWS 2
 #define MPE_CRYPTO_SPEAKER 2
-
-// where agent m's observation starts in the share row, and its width
-__host__ __device__ constexpr int mpe_crypto_obs_off(int m) { return m == 0 ? 0 : MPE_CRYPTO_OBS_E + (m - 1) * MPE_CRYPTO_OBS_B; }
-__host__ __device__ constexpr int mpe_crypto_obs_dim(int m) { return m == 0 ? MPE_CRYPTO_OBS_E : MPE_CRYPTO_OBS_B; }
 
 struct MpeCryptoArgs {
   int32_t *goal, *key;             // [N] landmark index of every agent's goal_a | of the speaker's key
@@ -149,3 +156,21 @@ __device__ __forceinline__ bool mpe_crypto_step_env(const MpeCryptoArgs &a, int 
   mpe_crypto_write_obs(o0, o1, o2, s);
   return done;
 }
+
+// What the shared kernels need of the scenario, in the one form they take it in.  obs_off / obs_dim: where agent m's observation
+// starts in the share row, and its width.  store's flag is `draws` here: the same role as the other scenarios' `landmarks`.
+struct MpeCrypto {
+  typedef MpeCryptoArgs Args;
+  typedef MpeCryptoState State;
+  static constexpr int M = MPE_CRYPTO_M, U = MPE_CRYPTO_C, SHARE = MPE_CRYPTO_SHARE;
+  __host__ __device__ static constexpr int obs_dim(int m) { return m == 0 ? MPE_CRYPTO_OBS_E : MPE_CRYPTO_OBS_B; }
+  __host__ __device__ static constexpr int obs_off(int m) { return m == 0 ? 0 : MPE_CRYPTO_OBS_E + (m - 1) * MPE_CRYPTO_OBS_B; }
+  static __device__ __forceinline__ void load(const Args &a, int n, State &s) { mpe_crypto_load(a, n, s); }
+  static __device__ __forceinline__ void store(const Args &a, int n, const State &s, bool draws) { mpe_crypto_store(a, n, s, draws); }
+  static __device__ __forceinline__ void reset_env(const Args &a, int n, State &s, int64_t ep) { mpe_crypto_reset_env(a, n, s, ep); }
+  static __device__ __forceinline__ void write_obs(float *const (&o)[M], const State &s) { mpe_crypto_write_obs(o[0], o[1], o[2], s); }
+  static __device__ __forceinline__ bool step_env(const Args &a, int n, const float *act, int act_stride, State &s, float *const (&o)[M],
+                                                  float (&reward)[M]) {
+    return mpe_crypto_step_env(a, n, act, act_stride, s, o[0], o[1], o[2], reward);
+  }
+};

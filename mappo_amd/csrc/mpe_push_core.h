@@ -1,7 +1,18 @@
 // mpe_push_core.h — the MPE `simple_push` ("keep-away") environment as device functions: reset, one environment step and the
-// observation write, one lane per environment.  Shared by the stepwise kernels (mpe_push_env.hip) and the one-launch rollout
-// episode (rollout_push.h), so a step computes the same float64 values whichever launch runs it.  Reference sites: see
-// mpe_push_env.hip.
+// observation write, one lane per environment, and the traits (MpePush, at the end) through which the shared kernels reach them: the
+// stepwise kernels (mpe_ragged_env.h) and the one-launch rollout episode (rollout_push.h), so a step computes the same float64 values
+// whichever launch runs it.
+//
+// Reference: onpolicy/envs/mpe/environment.py:194-256 (action decoding), :49-50,142 (world.collaborative is not set: per-agent
+// rewards), :179-185 (time-limit done); onpolicy/envs/mpe/core.py:207-322 (World.step: action force, the soft-collision force
+// between the two agents, damping, integration; no max_speed); onpolicy/envs/mpe/scenarios/simple_push.py:12-40 (both agents collide,
+// the landmarks do not), :42-65 (reset), :67-84 (reward), :86-107 (observation); and the reset-on-done of the vec-env wrappers
+// (envs/env_wrappers.py:146-152).
+//
+// Float64 as in the reference's NumPy code, contraction off.  Beside adds, multiplies and correctly rounded square roots the
+// contact force goes through exp and log1p, and the device's are not NumPy's, so outputs match the fp32 cast of the reference's
+// (tests/golden/mpe_push.npz) to 1e-6, not by construction to the bit.  State is device resident; resets draw from the
+// counter-based Philox stream keyed by (seed, episode, index) — index layout below.
 //
 // Fixed shape (num_agents = 2, num_landmarks = 2): agent 0 is the ADVERSARY (own velocity, the two landmarks and the other agent
 // relative to itself: 8 features; it is not told which landmark is the goal), agent 1 is the GOOD agent (own velocity, the goal
@@ -29,10 +40,6 @@
 #define MPE_PUSH_SHARE (MPE_PUSH_OBS_A + MPE_PUSH_OBS_G)            // the two observations side by side, adversary first: 27
 #define MPE_PUSH_DRAWS 16
 #define MPE_PUSH_SIZE 0.05                                          // both agents (core.py: the default entity size)
-
-// where agent m's observation starts in the share row, and its width
-__host__ __device__ constexpr int mpe_push_obs_off(int m) { return m == 0 ? 0 : MPE_PUSH_OBS_A; }
-__host__ __device__ constexpr int mpe_push_obs_dim(int m) { return m == 0 ? MPE_PUSH_OBS_A : MPE_PUSH_OBS_G; }
 
 struct MpePushArgs {
   double *apos, *avel, *lpos;      // agents [N][2][2], [N][2][2]; landmarks [N][2][2]
@@ -200,3 +207,21 @@ __device__ __forceinline__ bool mpe_push_step_env(const MpePushArgs &a, int n, c
   mpe_push_write_obs(oa, og, s);
   return done;
 }
+
+// What the shared kernels need of the scenario, in the one form they take it in.  obs_off / obs_dim: where agent m's observation
+// starts in the share row, and its width.
+struct MpePush {
+  typedef MpePushArgs Args;
+  typedef MpePushState State;
+  static constexpr int M = MPE_PUSH_M, U = MPE_PUSH_U, SHARE = MPE_PUSH_SHARE;
+  __host__ __device__ static constexpr int obs_dim(int m) { return m == 0 ? MPE_PUSH_OBS_A : MPE_PUSH_OBS_G; }
+  __host__ __device__ static constexpr int obs_off(int m) { return m == 0 ? 0 : MPE_PUSH_OBS_A; }
+  static __device__ __forceinline__ void load(const Args &a, int n, State &s) { mpe_push_load(a, n, s); }
+  static __device__ __forceinline__ void store(const Args &a, int n, const State &s, bool landmarks) { mpe_push_store(a, n, s, landmarks); }
+  static __device__ __forceinline__ void reset_env(const Args &a, int n, State &s, int64_t ep) { mpe_push_reset_env(a, n, s, ep); }
+  static __device__ __forceinline__ void write_obs(float *const (&o)[M], const State &s) { mpe_push_write_obs(o[0], o[1], s); }
+  static __device__ __forceinline__ bool step_env(const Args &a, int n, const float *act, int act_stride, State &s, float *const (&o)[M],
+                                                  float (&reward)[M]) {
+    return mpe_push_step_env(a, n, act, act_stride, s, o[0], o[1], reward);
+  }
+};

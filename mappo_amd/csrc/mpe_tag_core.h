@@ -1,6 +1,18 @@
 // mpe_tag_core.h — the MPE `simple_tag` (predator-prey) environment as device functions: reset, one environment step and the
-// observation write, one lane per environment.  Shared by every launch that steps this environment, so a step computes the same
-// float64 values whichever launch runs it.  Reference sites: see mpe_tag_env.hip.
+// observation write, one lane per environment, and the traits (MpeTag, at the end) through which the shared kernels reach them: the
+// stepwise kernels (mpe_ragged_env.h) and the one-launch rollout episode (rollout_tag.h), so a step computes the same float64 values
+// whichever launch runs it.
+//
+// Reference: onpolicy/envs/mpe/environment.py:194-256 (action decoding, accel in place of the sensitivity), :49-50,142
+// (world.collaborative is not set: per-agent rewards), :179-185 (time-limit done); onpolicy/envs/mpe/core.py:207-322 (World.step:
+// action force, soft-collision forces between every pair with a movable member, damping, the max_speed clamp, integration);
+// onpolicy/envs/mpe/scenarios/simple_tag.py:20-31 (sizes, accel, max_speed), :37-51 (reset), :81-126 (reward), :128-144 (observation);
+// and the reset-on-done of the vec-env wrappers (envs/env_wrappers.py:146-152).
+//
+// Float64 as in the reference's NumPy code, contraction off.  Unlike simple_adversary this step is not only adds, multiplies and
+// square roots: the contact force goes through exp and log1p and the boundary penalty through exp, and the device's are not NumPy's,
+// so outputs match the fp32 cast of the reference's (tests/golden/mpe_tag.npz) to 1e-6, not to the bit.  State is device resident;
+// resets draw from the counter-based Philox stream keyed by (seed, episode, index) — index layout below.
 //
 // Fixed shape (num_adversaries = 3, num_good_agents = 1, num_landmarks = 2): agents 0..2 are the ADVERSARIES (size 0.075, accel 3,
 // max_speed 1), agent 3 is the GOOD agent (size 0.05, accel 4, max_speed 1.3); the landmarks (size 0.2) collide and do not move.
@@ -29,9 +41,6 @@
 #define MPE_TAG_SHARE (3 * MPE_TAG_OBS_A + MPE_TAG_OBS_G)           // the four observations side by side, adversaries first: 62
 #define MPE_TAG_DRAWS 16
 
-// where agent m's observation starts in the share row, and its width
-__host__ __device__ constexpr int mpe_tag_obs_off(int m) { return m * MPE_TAG_OBS_A; }
-__host__ __device__ constexpr int mpe_tag_obs_dim(int m) { return m == MPE_TAG_GOOD ? MPE_TAG_OBS_G : MPE_TAG_OBS_A; }
 // per-agent physics (simple_tag.py:20-24) and the landmarks' size (:31)
 __host__ __device__ constexpr double mpe_tag_size(int m) { return m == MPE_TAG_GOOD ? 0.05 : 0.075; }
 __host__ __device__ constexpr double mpe_tag_accel(int m) { return m == MPE_TAG_GOOD ? 4.0 : 3.0; }
@@ -237,3 +246,21 @@ __device__ __forceinline__ bool mpe_tag_step_env(const MpeTagArgs &a, int n, con
   mpe_tag_write_obs(o0, o1, o2, o3, s);
   return done;
 }
+
+// What the shared kernels need of the scenario, in the one form they take it in.  obs_off / obs_dim: where agent m's observation
+// starts in the share row, and its width.
+struct MpeTag {
+  typedef MpeTagArgs Args;
+  typedef MpeTagState State;
+  static constexpr int M = MPE_TAG_M, U = MPE_TAG_U, SHARE = MPE_TAG_SHARE;
+  __host__ __device__ static constexpr int obs_dim(int m) { return m == MPE_TAG_GOOD ? MPE_TAG_OBS_G : MPE_TAG_OBS_A; }
+  __host__ __device__ static constexpr int obs_off(int m) { return m * MPE_TAG_OBS_A; }
+  static __device__ __forceinline__ void load(const Args &a, int n, State &s) { mpe_tag_load(a, n, s); }
+  static __device__ __forceinline__ void store(const Args &a, int n, const State &s, bool landmarks) { mpe_tag_store(a, n, s, landmarks); }
+  static __device__ __forceinline__ void reset_env(const Args &a, int n, State &s, int64_t ep) { mpe_tag_reset_env(a, n, s, ep); }
+  static __device__ __forceinline__ void write_obs(float *const (&o)[M], const State &s) { mpe_tag_write_obs(o[0], o[1], o[2], o[3], s); }
+  static __device__ __forceinline__ bool step_env(const Args &a, int n, const float *act, int act_stride, State &s, float *const (&o)[M],
+                                                  float (&reward)[M]) {
+    return mpe_tag_step_env(a, n, act, act_stride, s, o[0], o[1], o[2], o[3], reward);
+  }
+};

@@ -3,7 +3,7 @@
 // per-agent reward and SeparatedReplayBuffer.  It does what T x (two mappo_rollout_step + mappo_mpe_push_step + the two agents'
 // inserts) + the two bootstrap launches do, ~5 T + 2 dependent launches.
 //
-// The two-barrier skeleton of rollout_comm.h / rollout_adversary.h / rollout_tag.h (read their headers first): a tile is 16 whole
+// The two-barrier skeleton of rollout_comm.h / rollout_sep_img.h / rollout_tag.h (read their headers first): a tile is 16 whole
 // environments, one workgroup of FOUR waves per tile, one per SIMD, one row per environment and agent.  Two agents are four
 // networks, one per wave as in rollout_comm.h — but that kernel keeps all four in registers and steps the environments in a critic
 // wave's lanes, which at tanh / layer_N 1 already costs it 112 B of scratch with an env that has no float64 exp / log1p.  This env's
@@ -36,28 +36,26 @@
 
 typedef SepEpisodeArgs<MpePushArgs, MPE_PUSH_M> PushEpisodeArgs;      // agent 0: adversary, 1: good agent
 
-#define PUSH_EP_G 16                                                // environments per tile (workgroup)
-#define PUSH_EP_WAVES 4
 #define PUSH_X_TILE (16 * MPE_PUSH_SHARE)
 template <int LN>
-constexpr int push_ep_lds_floats() { return MPE_PUSH_M * EplMap<LN>::total + PUSH_X_TILE + PUSH_EP_WAVES * 16 * TP + MPE_PUSH_M * 16; }
+constexpr int push_ep_lds_floats() { return MPE_PUSH_M * EplMap<LN>::total + PUSH_X_TILE + SEP_EP_WAVES * 16 * TP + MPE_PUSH_M * 16; }
 
 template <bool RELU, int LN>
-__global__ __launch_bounds__(PUSH_EP_WAVES * WAVE, 1) void rollout_episode_push_kernel(PushEpisodeArgs e) {
+__global__ __launch_bounds__(SEP_EP_WAVES * WAVE, 1) void rollout_episode_push_kernel(PushEpisodeArgs e) {
   extern __shared__ __align__(16) float lds[];
   constexpr int IMG = EplMap<LN>::total, W = MPE_PUSH_SHARE;
-  float *X = lds + MPE_PUSH_M * IMG, *tZ = X + PUSH_X_TILE, *act = tZ + PUSH_EP_WAVES * 16 * TP;
+  float *X = lds + MPE_PUSH_M * IMG, *tZ = X + PUSH_X_TILE, *act = tZ + SEP_EP_WAVES * 16 * TP;
   const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), j = lane & 15, q = lane >> 4;
   const int T = e.T;
   const int64_t B = e.env.N;                                        // rows of every buffer: one per environment
-  const int n0 = (int)blockIdx.x * PUSH_EP_G;                       // first environment / buffer row of this tile
+  const int n0 = (int)blockIdx.x * SEP_EP_G;                        // first environment / buffer row of this tile
   const int64_t i = (int64_t)n0 + j;
   const bool ok = i < B;
   const int jr = ok ? j : 0;
   if (wave < MPE_PUSH_M) {
     // ---- agent m's actor (registers); step 0 reads buffer slot 0, as the stepwise path does ----
     const int m = wave;
-    const int D = mpe_push_obs_dim(m), xo = mpe_push_obs_off(m);
+    const int D = MpePush::obs_dim(m), xo = MpePush::obs_off(m);
     FwdArgs fa;
     comm_fwd_args(fa, e.a[m], B, e.deterministic);
     f32x4 xa[4];
@@ -82,10 +80,10 @@ __global__ __launch_bounds__(PUSH_EP_WAVES * WAVE, 1) void rollout_episode_push_
     // ---- agent m's critic (LDS image), its rows of the buffer's observations and, in wave 3's lanes 0 .. 15, the environments, the
     // state in the lane for the whole episode ----
     const int m = wave - MPE_PUSH_M;
-    const int D = mpe_push_obs_dim(m), xo = mpe_push_obs_off(m);
-    const bool env_wave = wave == PUSH_EP_WAVES - 1;
+    const int D = MpePush::obs_dim(m), xo = MpePush::obs_off(m);
+    const bool env_wave = wave == SEP_EP_WAVES - 1;
     const int n = n0 + lane;
-    const bool env_lane = env_wave && lane < PUSH_EP_G && n < e.env.N;
+    const bool env_lane = env_wave && lane < SEP_EP_G && n < e.env.N;
     const int Rv = (int)(B - n0 < 16 ? B - n0 : 16);                // rows of the tile that exist (the last tile may be partial)
     FwdArgs fc;
     comm_fwd_args(fc, e.c[m], B, 0);
@@ -105,10 +103,10 @@ __global__ __launch_bounds__(PUSH_EP_WAVES * WAVE, 1) void rollout_episode_push_
       asm volatile("" ::: "memory");        // the image is loop-invariant: keep its reads inside the step (hoisted, they are a register network)
       tile16r_step<RELU, LN, 0>(fc, cw, ch, xc, fc.out + so, nullptr, nullptr, 0ull, nullptr, tZ + wave * 16 * TP, i, ok, j, q);
       __syncthreads();                                              // A_t
-      if (env_lane) {       // obs -> the tile's row, each agent's own reward -> slot t, masks -> slot t + 1 of its buffer
+      if (env_lane) {       // sep_env_step, kept inline: through the shared function the register allocation moved and a rollout took 1.5 % longer
         float reward[MPE_PUSH_M];
         float *row = X + lane * W;
-        const bool done = mpe_push_step_env(e.env, n, act + lane, 16, s, row, row + mpe_push_obs_off(1), reward);
+        const bool done = mpe_push_step_env(e.env, n, act + lane, 16, s, row, row + MpePush::obs_off(1), reward);
 #pragma unroll
         for (int k = 0; k < MPE_PUSH_M; ++k) {
           e.rew_buf[k][so + n] = reward[k];
@@ -118,15 +116,7 @@ __global__ __launch_bounds__(PUSH_EP_WAVES * WAVE, 1) void rollout_episode_push_
       __syncthreads();                                              // B_t
       // what the stepwise insert writes into agent m's slot t + 1 (centralized: the tile's row as it stands); the next write of the
       // tile is behind A_{t + 1}, which this wave passes after the copy
-      float *od = e.obs_buf[m] + (so + B + n0) * D;
-      for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; od[k] = X[r * W + xo + (k - r * D)]; }
-      if (e.centralized) {
-        float *sd = e.share_buf[m] + (so + B + n0) * W;
-        for (int k = lane; k < Rv * W; k += WAVE) sd[k] = X[k];
-      } else {
-        float *sd = e.share_buf[m] + (so + B + n0) * D;
-        for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; sd[k] = X[r * W + xo + (k - r * D)]; }
-      }
+      sep_copy_rows<W>(e, X, m, D, xo, so + B + n0, Rv, lane);
       spread_load_x(xc, X + jr * W + so_x, S, q);
     }
     asm volatile("" ::: "memory");
@@ -134,6 +124,12 @@ __global__ __launch_bounds__(PUSH_EP_WAVES * WAVE, 1) void rollout_episode_push_
     if (env_lane) mpe_push_store(e.env, n, s, true);                // the environment continues from here in either path
   }
 }
+
+template <bool RELU, int LN>
+struct PushEpisode {
+  static constexpr auto kernel = rollout_episode_push_kernel<RELU, LN>;
+  static constexpr int lds_bytes = sizeof(float) * push_ep_lds_floats<LN>();
+};
 
 extern "C" int mappo_rollout_episode_push(const mappo_comm_agent *agents, double *agent_pos, double *agent_vel, double *landmark_pos,
                                           int32_t *goal, int32_t *tstep, int64_t *episode, int32_t T, int32_t N, int32_t env_episode_length,
@@ -149,12 +145,5 @@ extern "C" int mappo_rollout_episode_push(const mappo_comm_agent *agents, double
   MAPPO_CLEAR_STICKY();
   e.env.apos = agent_pos; e.env.avel = agent_vel; e.env.lpos = landmark_pos; e.env.goal = goal; e.env.tstep = tstep; e.env.episode = episode;
   e.env.N = N; e.env.T = env_episode_length; e.env.mode = 1; e.env.seed = env_seed;
-  const dim3 grid((unsigned)((N + PUSH_EP_G - 1) / PUSH_EP_G));
-  if (int rc = dispatch_relu_ln<1>(agents[0].actor_desc.use_relu != 0, agents[0].actor_desc.layer_N, [&](auto R, auto L) {
-        constexpr int lds_bytes = sizeof(float) * push_ep_lds_floats<L.value>();
-        return launch_kernel<rollout_episode_push_kernel<R.value, L.value>, lds_bytes>(who, grid, dim3(PUSH_EP_WAVES * WAVE), lds_bytes, as_stream(stream), e);
-      }))
-    return rc;
-  MAPPO_CHECK_LAUNCH(who);
-  return MAPPO_OK;
+  return sep_episode_launch<PushEpisode>(who, N, agents[0], e, stream);
 }

@@ -1,14 +1,22 @@
-// rollout_separated.h — what the one-launch episodes of the SEPARATED runner share (rollout_comm.h, rollout_adversary.h,
-// rollout_tag.h, rollout_push.h, rollout_crypto.h; rollout_world_comm.h uses the checks and the actors' half of the fill): M agents of different shapes, each with its own actor, critic and SeparatedReplayBuffer, on a
-// GPU-resident env whose steps run inside the launch.  The kernels differ — where the weights live and which wave steps the
-// environments; their headers say why — but around them they are one thing:
+// rollout_separated.h — what the one-launch episodes of the SEPARATED runner share (rollout_comm.h, rollout_sep_img.h, rollout_tag.h,
+// rollout_push.h; rollout_world_comm.h uses the checks and the actors' half of the fill): M agents of different shapes, each with its
+// own actor, critic and SeparatedReplayBuffer, on a GPU-resident env whose steps run inside the launch.  The kernels differ — where the
+// weights live and which wave steps the environments; their headers say why — but around them they are one thing:
 //   the argument block (SepEpisodeArgs: two CommNet per agent, the env's own args, the agents' buffer arrays);
 //   the host's checks of the M agent descriptors and the fill of that block (sep_episode_fill); an entry point adds its env state
-//   and launches through dispatch_relu_ln / launch_kernel (mlp_launch.h).
-// The row copy "what the stepwise insert writes" stays with each kernel: one shared function moved the comm kernel's register count.
+//   and launches through sep_episode_launch: one workgroup of SEP_EP_WAVES waves per tile of SEP_EP_G environments;
+//   for the scenarios with a traits struct (rollout_sep_img.h, rollout_tag.h, rollout_push.h), the two pieces of a step that touch
+//   the buffers: the row copy "what the stepwise insert writes" (sep_copy_rows) and the env lanes' step (sep_env_step; the tag and
+//   push kernels keep that block inline: through the function their register allocation moved and a rollout took ~2 % longer).
+// rollout_comm.h and rollout_world_comm.h keep their own inline copies of those two and of the launch tail: their environments have
+// another shape (one shared reward and split action pointers; a MultiDiscrete leader), and both kernels sit at the register limit —
+// the comm kernel with 112 B of scratch, where a shared row copy moved its register count.
 #pragma once
 #include "rollout_spread.h"
 #include <cstdio>
+
+#define SEP_EP_G 16                                                 // environments per tile (workgroup)
+#define SEP_EP_WAVES 4                                              // one per SIMD
 
 struct CommNet {                   // what tile16r_step reads of a FwdArgs, per network (2 M FwdArgs would not fit the kernel arguments)
   const float *params;
@@ -76,5 +84,54 @@ static int sep_episode_fill(SepEpisodeArgs<EnvArgs, M> &e, const char *who, cons
     e.next_values[m] = ag[m].next_values;
   }
   e.counter = counter; e.T = T; e.centralized = centralized; e.deterministic = deterministic;
+  return MAPPO_OK;
+}
+
+// What the stepwise insert writes into agent m's slot t + 1 (dst row offset `row0` = (t + 1) N + n0), by one whole wave: the agent's D
+// columns from xo of the observation tile X [16][W] -> obs, and the tile's whole row (centralized) or the same columns again ->
+// share_obs.  Rv: rows of the tile that exist.
+template <int W, class EnvArgs, int M>
+__device__ __forceinline__ void sep_copy_rows(const SepEpisodeArgs<EnvArgs, M> &e, const float *X, int m, int D, int xo, int64_t row0, int Rv,
+                                              int lane) {
+  float *od = e.obs_buf[m] + row0 * D;
+  for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; od[k] = X[r * W + xo + (k - r * D)]; }
+  if (e.centralized) {
+    float *sd = e.share_buf[m] + row0 * W;
+    for (int k = lane; k < Rv * W; k += WAVE) sd[k] = X[k];
+  } else {
+    float *sd = e.share_buf[m] + row0 * D;
+    for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; sd[k] = X[r * W + xo + (k - r * D)]; }
+  }
+}
+
+// The env lane's part of step t (so = t N), between the barriers A_t and B_t: environment n, whose state s the lane holds, takes the
+// agents' actions from column `lane` of the action tile, writes its observations into row `lane` of the tile X [16][Env::SHARE], each
+// agent's OWN reward into slot t of its buffer and 1 - done into slot t + 1.  Env: the scenario's traits (mpe_*_core.h).
+template <class Env>
+__device__ __forceinline__ void sep_env_step(const SepEpisodeArgs<typename Env::Args, Env::M> &e, int n, int64_t so, int64_t B,
+                                             typename Env::State &s, float *X, const float *act, int lane) {
+  float reward[Env::M];
+  float *o[Env::M];
+#pragma unroll
+  for (int k = 0; k < Env::M; ++k) o[k] = X + lane * Env::SHARE + Env::obs_off(k);
+  const bool done = Env::step_env(e.env, n, act + lane, 16, s, o, reward);
+#pragma unroll
+  for (int k = 0; k < Env::M; ++k) {
+    e.rew_buf[k][so + n] = reward[k];
+    e.mask_buf[k][so + B + n] = done ? 0.f : 1.f;
+  }
+}
+
+// The tail of an entry point: the grid, the (activation, layer_N) instantiation and the launch.  K<RELU, LN> names it: `kernel` and
+// its dynamic `lds_bytes`.  first: the descriptor all networks were checked against (sep_episode_fill).
+template <template <bool, int> class K, class Args>
+static int sep_episode_launch(const char *who, int32_t N, const mappo_comm_agent &first, const Args &e, mappo_stream_t stream) {
+  const dim3 grid((unsigned)((N + SEP_EP_G - 1) / SEP_EP_G));
+  if (int rc = dispatch_relu_ln<1>(first.actor_desc.use_relu != 0, first.actor_desc.layer_N, [&](auto R, auto L) {
+        typedef K<R.value, L.value> Inst;
+        return launch_kernel<Inst::kernel, Inst::lds_bytes>(who, grid, dim3(SEP_EP_WAVES * WAVE), Inst::lds_bytes, as_stream(stream), e);
+      }))
+    return rc;
+  MAPPO_CHECK_LAUNCH(who);
   return MAPPO_OK;
 }

@@ -3,8 +3,8 @@
 // per-agent reward and SeparatedReplayBuffer.  It does what T x (four mappo_rollout_step + mappo_mpe_tag_step + the four agents'
 // inserts) + the four bootstrap launches do, ~9 T + 4 dependent launches.
 //
-// The two-barrier skeleton of rollout_comm.h / rollout_adversary.h (read their headers first): a tile is 16 whole environments, one
-// workgroup of FOUR waves per tile, one per SIMD.  Eight networks do not fit the adversary's placement: four critic images of
+// The two-barrier skeleton of rollout_comm.h / rollout_sep_img.h (read their headers first): a tile is 16 whole environments, one
+// workgroup of FOUR waves per tile, one per SIMD.  Eight networks do not fit rollout_sep_img.h's placement: four critic images of
 // EplMap<1>::total = 11424 floats plus the tiles are ~191 KB against 160 KB of LDS, and a fifth wave for the environments would put
 // two waves on a SIMD and halve the register budget under an actor.  So here
 //   wave m = 0, 1, 2   adversary m, both networks.  Its ACTOR has its weights in registers (Trunk16R / Head16R; 16 inputs, so one of
@@ -18,8 +18,8 @@
 //           Order per step: actor, A_t, environments (mode 1; each agent's OWN reward -> its rew_buf[t], 1 - done -> its
 //           mask_buf[t + 1]), critic, B_t.
 // Every accessor struct returns the same 16-byte operands in the same order as Trunk16R, so tile16r_step computes the same bits.
-// Behind B_t every wave copies its own agent's rows of observation tile t + 1 into its obs[t + 1] / share_obs[t + 1] (what the
-// stepwise insert writes) and takes its next inputs from the tile.  A_t: the actions of step t are in LDS and every read of
+// Behind B_t every wave copies its own agent's rows of observation tile t + 1 into its obs[t + 1] / share_obs[t + 1] (sep_copy_rows: what
+// the stepwise insert writes) and takes its next inputs from the tile.  A_t: the actions of step t are in LDS and every read of
 // observation tile t is done; B_t: observation tile t + 1 is in LDS.  No wave returns early: one whose rows or lanes do not exist
 // (last partial tile) still walks all T steps and their barriers.
 //
@@ -122,27 +122,10 @@ __device__ __forceinline__ void tag_stage(float *img, const float *P, const NetO
 
 typedef SepEpisodeArgs<MpeTagArgs, MPE_TAG_M> TagEpisodeArgs;         // agents 0 .. 2: adversaries, 3: the good agent
 
-#define TAG_EP_G 16                                                 // environments per tile (workgroup)
-#define TAG_EP_WAVES 4
 #define TAG_X_TILE (16 * MPE_TAG_SHARE)
 template <int LN>
 constexpr int tag_ep_lds_floats() {
   return MPE_TAG_M * TagMap<LN>::total + EplMap<LN>::total + TAG_X_TILE + MPE_TAG_M * 16 * TP + MPE_TAG_M * 16 + MPE_TAG_GOOD * TAG_AVEC;
-}
-
-// what the stepwise insert writes into agent m's slot t + 1 (dst row offset `row0` = (t + 1) N + n0): its rows of the observation
-// tile -> obs, and the tile's whole row (centralized) or the same rows again -> share_obs
-__device__ __forceinline__ void tag_copy_rows(const TagEpisodeArgs &e, const float *X, int m, int D, int xo, int64_t row0, int Rv, int lane) {
-  constexpr int W = MPE_TAG_SHARE;
-  float *od = e.obs_buf[m] + row0 * D;
-  for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; od[k] = X[r * W + xo + (k - r * D)]; }
-  if (e.centralized) {
-    float *sd = e.share_buf[m] + row0 * W;
-    for (int k = lane; k < Rv * W; k += WAVE) sd[k] = X[k];
-  } else {
-    float *sd = e.share_buf[m] + row0 * D;
-    for (int k = lane; k < Rv * D; k += WAVE) { const int r = k / D; sd[k] = X[r * W + xo + (k - r * D)]; }
-  }
 }
 
 // the critic's W1 into the split trunk's registers, as trunk16r_load reads it
@@ -158,7 +141,7 @@ __device__ __forceinline__ void tag_load_w1(Trunk16S<LN> &cw, const FwdArgs &fc,
 }
 
 template <bool RELU, int LN>
-__global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_kernel(TagEpisodeArgs e) {
+__global__ __launch_bounds__(SEP_EP_WAVES * WAVE, 1) void rollout_episode_tag_kernel(TagEpisodeArgs e) {
   extern __shared__ __align__(16) float lds[];
   constexpr int IMG = TagMap<LN>::total, W = MPE_TAG_SHARE, G = MPE_TAG_GOOD;
   float *aimg = lds + MPE_TAG_M * IMG;                              // the good agent's actor, whole (EplMap)
@@ -166,7 +149,7 @@ __global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_ke
   const int lane = threadIdx.x & (WAVE - 1), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), j = lane & 15, q = lane >> 4;
   const int T = e.T;
   const int64_t B = e.env.N;                                        // rows of every buffer: one per environment
-  const int n0 = (int)blockIdx.x * TAG_EP_G;                        // first environment / buffer row of this tile
+  const int n0 = (int)blockIdx.x * SEP_EP_G;                        // first environment / buffer row of this tile
   const int64_t i = (int64_t)n0 + j;
   const bool ok = i < B;
   const int jr = ok ? j : 0;
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_ke
     // ---- adversary m: actor in registers, critic split; step 0 reads buffer slot 0, as the stepwise path does ----
     const int m = wave;
     constexpr int D = MPE_TAG_OBS_A;
-    const int xo = mpe_tag_obs_off(m);
+    const int xo = MpeTag::obs_off(m);
     FwdArgs fa, fc;
     comm_fwd_args(fa, e.a[m], B, e.deterministic);
     comm_fwd_args(fc, e.c[m], B, 0);
@@ -212,7 +195,7 @@ __global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_ke
       asm volatile("" ::: "memory");        // the image is loop-invariant: keep its reads inside the step (hoisted, they are a second register network)
       tile16r_step<RELU, LN, 0>(fc, cw, ch, xc, fc.out + so, nullptr, nullptr, 0ull, nullptr, tZ + m * 16 * TP, i, ok, j, q);
       __syncthreads();                                              // B_t
-      tag_copy_rows(e, X, m, D, xo, so + B + n0, Rv, lane);         // the tile's next write is behind A_{t + 1}, which this wave reaches after these reads
+      sep_copy_rows<W>(e, X, m, D, xo, so + B + n0, Rv, lane);      // the tile's next write is behind A_{t + 1}, which this wave reaches after these reads
       spread_load_x(xa, X + jr * W + xo, D, q);
       spread_load_x(xc, X + jr * W + so_x, S, q);
     }
@@ -221,9 +204,9 @@ __global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_ke
   } else {
     // ---- the good agent — actor from its LDS image, critic split — and, in lanes 0 .. 15, the environments: the state stays in the
     // lane for the whole episode ----
-    constexpr int m = G, D = MPE_TAG_OBS_G, xo = mpe_tag_obs_off(G);
+    constexpr int m = G, D = MPE_TAG_OBS_G, xo = MpeTag::obs_off(G);
     const int n = n0 + lane;
-    const bool env_lane = lane < TAG_EP_G && n < e.env.N;
+    const bool env_lane = lane < SEP_EP_G && n < e.env.N;
     MpeTagState s = {};
     if (env_lane) mpe_tag_load(e.env, n, s);
     FwdArgs fa, fc;
@@ -251,11 +234,11 @@ __global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_ke
       tile16r_step<RELU, LN, 1, false, true>(fa, tw, hd, xa, nullptr, fa.actions + so, fa.logp + so, ctr0 + (uint64_t)t, nullptr,
                                              tZ + m * 16 * TP, i, ok, j, q, act + m * 16);
       __syncthreads();                                              // A_t
-      if (env_lane) {       // obs -> the tile's row, each agent's own reward -> slot t, masks -> slot t + 1 of its buffer
+      if (env_lane) {       // sep_env_step, kept inline: through the shared function the register allocation moved and a rollout took 2 % longer
         float reward[MPE_TAG_M];
         float *row = X + lane * W;
-        const bool done = mpe_tag_step_env(e.env, n, act + lane, 16, s, row, row + mpe_tag_obs_off(1), row + mpe_tag_obs_off(2),
-                                           row + mpe_tag_obs_off(3), reward);
+        const bool done = mpe_tag_step_env(e.env, n, act + lane, 16, s, row, row + MpeTag::obs_off(1), row + MpeTag::obs_off(2),
+                                           row + MpeTag::obs_off(3), reward);
 #pragma unroll
         for (int k = 0; k < MPE_TAG_M; ++k) {
           e.rew_buf[k][so + n] = reward[k];
@@ -265,7 +248,7 @@ __global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_ke
       asm volatile("" ::: "memory");
       tile16r_step<RELU, LN, 0>(fc, cw, ch, xc, fc.out + so, nullptr, nullptr, 0ull, nullptr, tZ + m * 16 * TP, i, ok, j, q);
       __syncthreads();                                              // B_t
-      tag_copy_rows(e, X, m, D, xo, so + B + n0, Rv, lane);
+      sep_copy_rows<W>(e, X, m, D, xo, so + B + n0, Rv, lane);
       spread_load_x(xa, X + jr * W + xo, D, q);
       spread_load_x(xc, X + jr * W + so_x, S, q);
     }
@@ -274,6 +257,12 @@ __global__ __launch_bounds__(TAG_EP_WAVES * WAVE, 1) void rollout_episode_tag_ke
     if (env_lane) mpe_tag_store(e.env, n, s, true);                 // the environment continues from here in either path
   }
 }
+
+template <bool RELU, int LN>
+struct TagEpisode {
+  static constexpr auto kernel = rollout_episode_tag_kernel<RELU, LN>;
+  static constexpr int lds_bytes = sizeof(float) * tag_ep_lds_floats<LN>();
+};
 
 extern "C" int mappo_rollout_episode_tag(const mappo_comm_agent *agents, double *agent_pos, double *agent_vel, double *landmark_pos,
                                          int32_t *tstep, int64_t *episode, int32_t T, int32_t N, int32_t env_episode_length,
@@ -289,12 +278,5 @@ extern "C" int mappo_rollout_episode_tag(const mappo_comm_agent *agents, double 
   MAPPO_CLEAR_STICKY();
   e.env.apos = agent_pos; e.env.avel = agent_vel; e.env.lpos = landmark_pos; e.env.tstep = tstep; e.env.episode = episode;
   e.env.N = N; e.env.T = env_episode_length; e.env.mode = 1; e.env.seed = env_seed;
-  const dim3 grid((unsigned)((N + TAG_EP_G - 1) / TAG_EP_G));
-  if (int rc = dispatch_relu_ln<1>(agents[0].actor_desc.use_relu != 0, agents[0].actor_desc.layer_N, [&](auto R, auto L) {
-        constexpr int lds_bytes = sizeof(float) * tag_ep_lds_floats<L.value>();
-        return launch_kernel<rollout_episode_tag_kernel<R.value, L.value>, lds_bytes>(who, grid, dim3(TAG_EP_WAVES * WAVE), lds_bytes, as_stream(stream), e);
-      }))
-    return rc;
-  MAPPO_CHECK_LAUNCH(who);
-  return MAPPO_OK;
+  return sep_episode_launch<TagEpisode>(who, N, agents[0], e, stream);
 }
