@@ -661,7 +661,7 @@ int mappo_rollout_episode_comm(const mappo_comm_agent *speaker /*host*/, const m
                                int32_t deterministic, uint64_t counter, int32_t centralized,
                                mappo_stream_t stream);
 
-/* GPU-vectorised MPE simple_adversary, "physical deception" (csrc/mpe_adv_env.hip, device functions in csrc/mpe_adv_core.h): N
+/* GPU-vectorised MPE simple_adversary, "physical deception" (csrc/mpe_ragged_env.hip, device functions in csrc/mpe_adv_core.h): N
  * environments of the fixed shape num_agents = 3 — agent 0 the ADVERSARY (observes the 2 landmarks relative to itself 4, the two
  * others relative to itself 4 = 8 features; it is not told which landmark is the goal), agents 1 and 2 the GOOD agents (the goal
  * landmark relative to themselves 2, then the same 8 = 10 features), 2 landmarks; every agent moves, Discrete(5); nobody speaks,
@@ -689,7 +689,7 @@ int mappo_mpe_adversary_step(double *agent_pos, double *agent_vel, double *landm
                              float *obs_good2, float *rewards, uint8_t *dones, int32_t N, int32_t num_agents,
                              int32_t episode_length, uint64_t seed, mappo_stream_t stream);
 /* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner
- * (csrc/rollout_adversary.h): what T x (one mappo_rollout_step per agent + mappo_mpe_adversary_step with action_mode 1 + the
+ * (csrc/rollout_sep_img.h): what T x (one mappo_rollout_step per agent + mappo_mpe_adversary_step with action_mode 1 + the
  * agents' inserts) + one bootstrap mappo_rollout_step per agent do, bit for bit.  agents: the three mappo_comm_agent above
  * (adversary, good agent 1, good agent 2).  Per step t < T: agent m's actor on its observation rows of step t (step 0: obs_buf
  * slot 0), row n sampled with (agent's seed, counter + t (+ the agent's *counter_dev), Philox index n) -> actions / logp slot t;
@@ -705,7 +705,7 @@ int mappo_rollout_episode_adversary(const mappo_comm_agent *agents /*host, [3]*/
                                     int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                                     int32_t centralized, mappo_stream_t stream);
 
-/* GPU-vectorised MPE simple_tag, predator-prey (csrc/mpe_tag_env.hip, device functions in csrc/mpe_tag_core.h): N environments of
+/* GPU-vectorised MPE simple_tag, predator-prey (csrc/mpe_ragged_env.hip, device functions in csrc/mpe_tag_core.h): N environments of
  * the fixed shape num_adversaries = 3, num_good_agents = 1, num_landmarks = 2 (num_agents = 4) — agents 0..2 the ADVERSARIES (size
  * 0.075, accel 3, max_speed 1), agent 3 the GOOD agent (size 0.05, accel 4, max_speed 1.3), landmarks of size 0.2 that collide and
  * do not move; every agent moves, Discrete(5); nobody speaks — one launch per step.  Observation of agent m: own velocity 2, own
@@ -751,7 +751,7 @@ int mappo_rollout_episode_tag(const mappo_comm_agent *agents /*host, [4]*/, doub
                               int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                               int32_t centralized, mappo_stream_t stream);
 
-/* GPU-vectorised MPE simple_push, "keep-away" (csrc/mpe_push_env.hip, device functions in csrc/mpe_push_core.h): N environments of
+/* GPU-vectorised MPE simple_push, "keep-away" (csrc/mpe_ragged_env.hip, device functions in csrc/mpe_push_core.h): N environments of
  * the fixed shape num_agents = 2, num_landmarks = 2 — agent 0 the ADVERSARY (own velocity 2, the 2 landmarks relative to itself 4,
  * the other agent relative to itself 2 = 8 features; it is not told which landmark is the goal), agent 1 the GOOD agent (own
  * velocity 2, the goal relative to itself 2, its own colour 3, the 2 landmarks relative to itself 4, the landmarks' colours 6, the
@@ -796,7 +796,7 @@ int mappo_rollout_episode_push(const mappo_comm_agent *agents /*host, [2]*/, dou
                                int32_t env_episode_length, uint64_t env_seed, int32_t deterministic, uint64_t counter,
                                int32_t centralized, mappo_stream_t stream);
 
-/* GPU-vectorised MPE simple_crypto (csrc/mpe_crypto_env.hip, device functions in csrc/mpe_crypto_core.h): N environments of
+/* GPU-vectorised MPE simple_crypto (csrc/mpe_ragged_env.hip, device functions in csrc/mpe_crypto_core.h): N environments of
  * num_agents = 3 and num_landmarks L = 2, 3 or 4 — agent 0 the ADVERSARY "Eve" (observes what the speaker said: 4 features), agent 1
  * the good listener "Bob" (the key, then what the speaker said: 8), agent 2 the SPEAKER "Alice" (the goal, then the key: 8).  Nobody
  * moves and nothing collides; every agent only speaks, Discrete(4) = dim_c, and landmark k's colour is the one-hot e_k of R^4 — one
@@ -823,7 +823,7 @@ int mappo_mpe_crypto_step(int32_t *goal, int32_t *key, int32_t *comm, int32_t *t
                           int32_t action_mode, float *obs_eve, float *obs_bob, float *obs_alice, float *rewards, uint8_t *dones,
                           int32_t N, int32_t num_agents, int32_t num_landmarks, int32_t episode_length, uint64_t seed,
                           mappo_stream_t stream);
-/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner (csrc/rollout_crypto.h):
+/* One launch per rollout EPISODE on the environment above, env steps included, for the SEPARATED runner (csrc/rollout_sep_img.h):
  * what T x (one mappo_rollout_step per agent + mappo_mpe_crypto_step with action_mode 1 + the agents' inserts) + one bootstrap
  * mappo_rollout_step per agent do, bit for bit.  agents: three mappo_comm_agent (Eve, Bob, Alice).  Per step t < T: agent m's actor
  * on its observation rows of step t (step 0: obs_buf slot 0), row n sampled with (agent's seed, counter + t (+ the agent's

@@ -9,9 +9,9 @@ beyond 4 the reference itself raises an IndexError).  Agent 0, the adversary "Ev
 listener "Bob", also holds the key; agent 2, the speaker "Alice", sees the goal and the key.  Nobody moves: every agent only says one
 of `dim_c` = 4 symbols (Discrete(4)), and landmark k's colour is the one-hot e_k.  The world is not collaborative, so `rewards[:, m]`
 is agent m's OWN reward: with d(a) = |c_a - e_goal|^2, Eve gets -d(Eve), Bob and Alice d(Eve) - d(Bob) — every value -2, 0 or 2.
-The two observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_crypto_env.hip)
-and everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`,
-mappo_rollout_episode_crypto).  What the envs of this kind share is in mpe_ragged.py.
+The two observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_ragged_env.hip
+on csrc/mpe_crypto_core.h) and everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`,
+mappo_rollout_episode_crypto).  What the six envs of this kind share — all but the description below — is in mpe_ragged.py.
 
 `step` takes a list of per-agent tensors — each the reference's one-hot `[N, 4]` or indices `[N]` / `[N, 1]` — or one tensor: the
 one-hots `[N, 3, 4]` or, with `accepts_index_actions`, indices `[N, 3]` / `[N, 3, 1]`.  The whole state is integers (goal, key, the
@@ -20,28 +20,27 @@ symbol each agent last said), every output is a one-hot, zeros or -2 / 0 / 2, an
 generator."""
 import torch
 
-from .. import ops
-from .mpe_ragged import RaggedMPEVecEnv
+from .mpe_ragged import I32, I64, RaggedMPEVecEnv
 
 
 class SimpleCryptoVecEnv(RaggedMPEVecEnv):
-    M, C = 3, 4
+    scenario, M, C = "simple_crypto", 3, 4
     obs_dims, act_dims = (4, 8, 8), (4, 4, 4)
     episode_flag = "MAPPO_CRYPTO_EPISODE"
+    state = (("goal", I32, (), 0),                                 # landmark index of every agent's goal_a
+             ("key", I32, (), 0),                                  # landmark index of the speaker's key
+             ("comm", I32, (M,), -1),                              # the symbol each agent last said, -1: nothing said
+             ("tstep", I32, (), 0), ("episode", I64, (), 0))
+    env_ops = ("mpe_crypto_reset", "mpe_crypto_step", "rollout_episode_crypto")
+    shape_args, episode_shape_args = ("M", "L"), ("L",)            # L, this env's num_landmarks, is the instance's
 
     def __init__(self, n_rollout_threads, num_agents=3, num_landmarks=2, episode_length=25, seed=1, device="cuda"):
         if int(num_agents) != 3 or not 2 <= int(num_landmarks) <= 4:
             raise ValueError(f"simple_crypto is built for num_agents = 3 (adversary Eve, listener Bob, speaker Alice) and num_landmarks = 2, "
                              f"3 or 4, a landmark's colour being a one-hot of dim_c = 4 (got num_agents {num_agents}, num_landmarks "
                              f"{num_landmarks})")
-        super().__init__(n_rollout_threads, episode_length, seed, device)
         self.L = int(num_landmarks)
-        i32 = dict(dtype=torch.int32, device=self.device)
-        self.goal = torch.zeros(self.N, **i32)                     # landmark index of every agent's goal_a
-        self.key = torch.zeros(self.N, **i32)                      # landmark index of the speaker's key
-        self.comm = torch.full((self.N, self.M), -1, **i32)        # the symbol each agent last said, -1: nothing said
-        self.tstep = torch.zeros(self.N, **i32)
-        self.episode = torch.zeros(self.N, dtype=torch.int64, device=self.device)
+        super().__init__(n_rollout_threads, episode_length, seed, device)
 
     def set_state(self, goal, key, comm=-1, tstep=0):
         """Test hook: load explicit states (goal, key [N] landmark indices 0 .. L - 1; comm [N, 3] symbols 0 .. 3 or -1 for an
@@ -57,22 +56,3 @@ class SimpleCryptoVecEnv(RaggedMPEVecEnv):
         self.key.copy_(k)
         self.comm.copy_(c)
         self.tstep.fill_(int(tstep))
-
-    def state_tensors(self):
-        return dict(goal=self.goal, key=self.key, comm=self.comm, tstep=self.tstep, episode=self.episode)
-
-    def episode_launch(self, agents, T, deterministic, counter, centralized):
-        ops.rollout_episode_crypto(agents, T, self.N, self.T, self.seed, self.goal, self.key, self.comm, self.tstep, self.episode,
-                                   deterministic, counter, centralized, self.L)
-
-    def reset(self):
-        obs = self._next_out()[:3]
-        ops.mpe_crypto_reset(self.goal, self.key, self.comm, self.tstep, self.episode, *obs, self.N, self.seed, self.M, self.L)
-        return list(obs)
-
-    def step(self, actions):
-        mode, act = self._parse_actions(actions)
-        o0, o1, o2, rew, dones = self._next_out()
-        ops.mpe_crypto_step(self.goal, self.key, self.comm, self.tstep, self.episode, act, mode, o0, o1, o2, rew.view(self.N, self.M),
-                            dones.view(torch.uint8), self.N, self.T, self.seed, self.M, self.L)
-        return [o0, o1, o2], rew, dones, None

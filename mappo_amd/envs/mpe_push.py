@@ -10,9 +10,9 @@ velocity, the two landmarks and the other agent but not which landmark is the go
 the good agent is; agent 1, the good agent, also sees the goal, its own colour (which names the goal) and the landmarks' colours,
 and is paid for being near the goal.  The two agents collide with each other — the adversary pushes the good agent away — and with
 nothing else.  Both move (Discrete(5)).  The world is not collaborative, so `rewards[:, m]` is agent m's OWN reward.  The two
-observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_push_env.hip) and
-everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`, mappo_rollout_episode_push).
-What the envs of this kind share is in mpe_ragged.py.
+observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_ragged_env.hip on
+csrc/mpe_push_core.h) and everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`,
+mappo_rollout_episode_push).  What the six envs of this kind share — all but the description below — is in mpe_ragged.py.
 
 `step` takes a list of per-agent tensors — each the reference's one-hot `[N, 5]` or indices `[N]` / `[N, 1]` — or one tensor: the
 one-hots `[N, 2, 5]` or, with `accepts_index_actions`, indices `[N, 2]` / `[N, 2, 1]`.  Physics run in float64 as in the
@@ -21,28 +21,23 @@ goes through exp and log, which are not NumPy's to the bit); initial states come
 env), not from NumPy's global generator."""
 import torch
 
-from .. import ops
-from .mpe_ragged import RaggedMPEVecEnv
+from .mpe_ragged import F64, I32, I64, RaggedMPEVecEnv
 
 
 class SimplePushVecEnv(RaggedMPEVecEnv):
-    M, L = 2, 2
+    scenario, M, L = "simple_push", 2, 2
     obs_dims, act_dims = (8, 19), (5, 5)
     episode_flag = "MAPPO_PUSH_EPISODE"
+    state = (("agent_pos", F64, (M, 2), 0), ("agent_vel", F64, (M, 2), 0), ("landmark_pos", F64, (L, 2), 0),
+             ("goal", I32, (), 0),                                 # landmark index of both agents' goal_a
+             ("tstep", I32, (), 0), ("episode", I64, (), 0))
+    env_ops = ("mpe_push_reset", "mpe_push_step", "rollout_episode_push")
 
     def __init__(self, n_rollout_threads, num_agents=2, episode_length=25, seed=1, device="cuda", num_landmarks=2):
         if (int(num_agents), int(num_landmarks)) != (2, 2):
             raise ValueError(f"simple_push is built for num_agents = 2: 1 adversary, 1 good agent, 2 landmarks (got num_agents {num_agents}, "
                              f"num_landmarks {num_landmarks})")
         super().__init__(n_rollout_threads, episode_length, seed, device)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
-        self.agent_pos = torch.zeros(self.N, self.M, 2, **f64)
-        self.agent_vel = torch.zeros(self.N, self.M, 2, **f64)
-        self.landmark_pos = torch.zeros(self.N, self.L, 2, **f64)
-        self.goal = torch.zeros(self.N, **i32)                     # landmark index of both agents' goal_a
-        self.tstep = torch.zeros(self.N, **i32)
-        self.episode = torch.zeros(self.N, dtype=torch.int64, device=self.device)
 
     def set_state(self, agent_pos, agent_vel, landmark_pos, goal, tstep=0):
         """Test hook: load explicit states (float64 arrays / tensors [N, 2, 2], [N, 2, 2], [N, 2, 2]; goal [N] landmark indices).
@@ -55,24 +50,3 @@ class SimplePushVecEnv(RaggedMPEVecEnv):
             raise ValueError("goal must be landmark indices 0 .. 1")
         self.goal.copy_(g)
         self.tstep.fill_(int(tstep))
-
-    def state_tensors(self):
-        return dict(agent_pos=self.agent_pos, agent_vel=self.agent_vel, landmark_pos=self.landmark_pos, goal=self.goal, tstep=self.tstep,
-                    episode=self.episode)
-
-    def episode_launch(self, agents, T, deterministic, counter, centralized):
-        ops.rollout_episode_push(agents, T, self.N, self.T, self.seed, self.agent_pos, self.agent_vel, self.landmark_pos, self.goal,
-                                 self.tstep, self.episode, deterministic, counter, centralized)
-
-    def reset(self):
-        obs = self._next_out()[:2]
-        ops.mpe_push_reset(self.agent_pos, self.agent_vel, self.landmark_pos, self.goal, self.tstep, self.episode, *obs, self.N, self.seed,
-                           self.M)
-        return list(obs)
-
-    def step(self, actions):
-        mode, act = self._parse_actions(actions)
-        o0, o1, rew, dones = self._next_out()
-        ops.mpe_push_step(self.agent_pos, self.agent_vel, self.landmark_pos, self.goal, self.tstep, self.episode, act, mode, o0, o1,
-                          rew.view(self.N, self.M), dones.view(torch.uint8), self.N, self.T, self.seed, self.M)
-        return [o0, o1], rew, dones, None

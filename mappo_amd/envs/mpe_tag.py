@@ -9,9 +9,9 @@ DIFFERENT rewards:
 slower adversaries, are paid 10 for every adversary touching the good agent; agent 3, the faster and smaller good agent, loses 10 per
 contact and pays for leaving the arena.  Agents collide with each other and with the two landmarks, and each has its own accel,
 max_speed and size.  Every agent moves (Discrete(5)).  The world is not collaborative, so `rewards[:, m]` is agent m's OWN reward.
-The two observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_tag_env.hip) and
-everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`, mappo_rollout_episode_tag).
-What the three envs of this kind share is in mpe_ragged.py.
+The two observation widths force `share_policy = False`.  N environments are stepped by ONE kernel launch (csrc/mpe_ragged_env.hip
+on csrc/mpe_tag_core.h) and everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`,
+mappo_rollout_episode_tag).  What the six envs of this kind share — all but the description below — is in mpe_ragged.py.
 
 `step` takes a list of per-agent tensors — each the reference's one-hot `[N, 5]` or indices `[N]` / `[N, 1]` — or one tensor: the
 one-hots `[N, 4, 5]` or, with `accepts_index_actions`, indices `[N, 4]` / `[N, 4, 1]`.  Physics run in float64 as in the
@@ -20,14 +20,17 @@ goes through exp and log, which are not NumPy's to the bit); initial states come
 env), not from NumPy's global generator."""
 import torch
 
-from .. import ops
-from .mpe_ragged import RaggedMPEVecEnv
+from .mpe_ragged import F64, I32, I64, RaggedMPEVecEnv
 
 
 class SimpleTagVecEnv(RaggedMPEVecEnv):
-    M, L = 4, 2
+    scenario, M, L = "simple_tag", 4, 2
     obs_dims, act_dims = (16, 16, 16, 14), (5, 5, 5, 5)
     episode_flag = "MAPPO_TAG_EPISODE"
+    state = (("agent_pos", F64, (M, 2), 0), ("agent_vel", F64, (M, 2), 0), ("landmark_pos", F64, (L, 2), 0), ("tstep", I32, (), 0),
+             ("episode", I64, (), 0))
+    env_ops = ("mpe_tag_reset", "mpe_tag_step", "rollout_episode_tag")
+    episode_state_tag = RaggedMPEVecEnv.episode_state             # the name this scenario's tests call
 
     def __init__(self, n_rollout_threads, num_agents=4, episode_length=25, seed=1, device="cuda", num_adversaries=3, num_good_agents=1,
                  num_landmarks=2):
@@ -35,12 +38,6 @@ class SimpleTagVecEnv(RaggedMPEVecEnv):
             raise ValueError(f"simple_tag is built for num_agents = 4: 3 adversaries, 1 good agent, 2 landmarks (got num_agents {num_agents}, "
                              f"num_adversaries {num_adversaries}, num_good_agents {num_good_agents}, num_landmarks {num_landmarks})")
         super().__init__(n_rollout_threads, episode_length, seed, device)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        self.agent_pos = torch.zeros(self.N, self.M, 2, **f64)
-        self.agent_vel = torch.zeros(self.N, self.M, 2, **f64)
-        self.landmark_pos = torch.zeros(self.N, self.L, 2, **f64)
-        self.tstep = torch.zeros(self.N, dtype=torch.int32, device=self.device)
-        self.episode = torch.zeros(self.N, dtype=torch.int64, device=self.device)
 
     def set_state(self, agent_pos, agent_vel, landmark_pos, tstep=0):
         """Test hook: load explicit states (float64 arrays / tensors [N, 4, 2], [N, 4, 2], [N, 2, 2]).  `episode`, the reset counter
@@ -49,28 +46,3 @@ class SimpleTagVecEnv(RaggedMPEVecEnv):
         self.agent_vel.copy_(torch.as_tensor(agent_vel, dtype=torch.float64))
         self.landmark_pos.copy_(torch.as_tensor(landmark_pos, dtype=torch.float64))
         self.tstep.fill_(int(tstep))
-
-    def state_tensors(self):
-        return dict(agent_pos=self.agent_pos, agent_vel=self.agent_vel, landmark_pos=self.landmark_pos, tstep=self.tstep, episode=self.episode)
-
-    def episode_state_tag(self):
-        """The capability behind the separated runner's one-launch episode on THIS env (mappo_rollout_episode_tag steps the
-        environments inside the rollout kernel): the five state tensors, which that launch reads and stores back, and what it needs
-        to step them."""
-        return dict(scenario="simple_tag", N=self.N, M=self.M, L=self.L, T=self.T, seed=self.seed, **self.state_tensors())
-
-    def episode_launch(self, agents, T, deterministic, counter, centralized):
-        ops.rollout_episode_tag(agents, T, self.N, self.T, self.seed, self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep,
-                                self.episode, deterministic, counter, centralized)
-
-    def reset(self):
-        obs = self._next_out()[:4]
-        ops.mpe_tag_reset(self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep, self.episode, *obs, self.N, self.seed, self.M)
-        return list(obs)
-
-    def step(self, actions):
-        mode, act = self._parse_actions(actions)
-        o0, o1, o2, o3, rew, dones = self._next_out()
-        ops.mpe_tag_step(self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep, self.episode, act, mode, o0, o1, o2, o3,
-                         rew.view(self.N, self.M), dones.view(torch.uint8), self.N, self.T, self.seed, self.M)
-        return [o0, o1, o2, o3], rew, dones, None

@@ -15,7 +15,7 @@ observation widths force `share_policy = False`.  N environments are stepped by 
 everything stays in HBM, so the separated runner can run an episode as one launch (`episode_launch`, an attribute the env has only then,
 mappo_rollout_episode_world_comm: the six actors and the env steps; the critics run once afterwards, `episode_critics_after`).  That
 path is opt-in, MAPPO_WORLD_COMM_EPISODE=1 (`episode_default` is "0"): it samples with the one-launch step's arithmetic, which is not
-the stepwise collect's to the bit.  What the envs of this kind share is in mpe_ragged.py.
+the stepwise collect's to the bit.  What the six envs of this kind share is in mpe_ragged.py.
 
 `step` takes
   * the reference's one-hots as a per-agent list: `[N, 9]` for the leader (its two heads side by side), `[N, 5]` for the others;
@@ -29,14 +29,16 @@ import os
 
 import torch
 
-from .. import ops
 from ..utils.util import Discrete, MultiDiscrete
-from .mpe_ragged import RaggedMPEVecEnv
+from .mpe_ragged import F64, I32, I64, RaggedMPEVecEnv
 
 
 class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
-    M, L = 6, 5                                                     # L: landmark, food0, food1, forest0, forest1
+    scenario, M, L = "simple_world_comm", 6, 5                      # L: landmark, food0, food1, forest0, forest1
     obs_dims, act_dims = (34, 34, 34, 34, 28, 28), (9, 5, 5, 5, 5, 5)
+    state = (("agent_pos", F64, (M, 2), 0), ("agent_vel", F64, (M, 2), 0), ("landmark_pos", F64, (L, 2), 0), ("tstep", I32, (), 0),
+             ("episode", I64, (), 0))
+    env_ops = ("mpe_world_comm_reset", "mpe_world_comm_step", "rollout_episode_world_comm")
     accepts_multidiscrete_agents = True                             # step takes K index columns / K one-hots side by side per such agent
     episode_flag = "MAPPO_WORLD_COMM_EPISODE"                       # "1": the separated runner's one-launch episode; unset / "0": stepwise
     episode_default = "0"                                           # opt-in: the stepwise collect does not sample with the launch's bits
@@ -50,12 +52,6 @@ class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
                              f"{num_good_agents}, num_landmarks {num_landmarks})")
         super().__init__(n_rollout_threads, episode_length, seed, device)
         self.action_space = [MultiDiscrete([[0, 4], [0, 3]])] + [Discrete(5) for _ in range(self.M - 1)]      # environment.py:62-90
-        f64 = dict(dtype=torch.float64, device=self.device)
-        self.agent_pos = torch.zeros(self.N, self.M, 2, **f64)
-        self.agent_vel = torch.zeros(self.N, self.M, 2, **f64)
-        self.landmark_pos = torch.zeros(self.N, self.L, 2, **f64)
-        self.tstep = torch.zeros(self.N, dtype=torch.int32, device=self.device)
-        self.episode = torch.zeros(self.N, dtype=torch.int64, device=self.device)
 
     def set_state(self, agent_pos, agent_vel, landmark_pos, tstep=0):
         """Test hook: load explicit states (float64 arrays / tensors [N, 6, 2], [N, 6, 2], [N, 5, 2]).  `episode`, the reset counter
@@ -64,9 +60,6 @@ class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
         self.agent_vel.copy_(torch.as_tensor(agent_vel, dtype=torch.float64))
         self.landmark_pos.copy_(torch.as_tensor(landmark_pos, dtype=torch.float64))
         self.tstep.fill_(int(tstep))
-
-    def state_tensors(self):
-        return dict(agent_pos=self.agent_pos, agent_vel=self.agent_vel, landmark_pos=self.landmark_pos, tstep=self.tstep, episode=self.episode)
 
     @property
     def episode_launch(self):
@@ -78,11 +71,10 @@ class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
         class always shows the property (scripts/time_separated_episode.py asks the class)."""
         if os.environ.get(self.episode_flag, self.episode_default) == "0":
             raise AttributeError("episode_launch: the one-launch episode of simple_world_comm is opt-in (MAPPO_WORLD_COMM_EPISODE=1)")
-        return self._episode_launch
+        return super().episode_launch
 
-    def _episode_launch(self, agents, T, deterministic, counter, centralized):
-        ops.rollout_episode_world_comm(agents, T, self.N, self.T, self.seed, self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep,
-                                       self.episode, deterministic, counter, centralized)
+    def _obs_args(self, obs):
+        return (obs,)                                               # six outputs: the entry points take them as one pointer array
 
     def _bad_actions(self, what):
         return ValueError(f"{type(self).__name__}.step: {what}: expected a list of 6 per-agent tensors — one-hots [N, 9] (the leader's move "
@@ -106,16 +98,3 @@ class SimpleWorldCommVecEnv(RaggedMPEVecEnv):
         if tuple(a.shape) == (N, M + 1):
             return 1, a.contiguous()
         raise self._bad_actions(f"actions of shape {tuple(a.shape)}")
-
-    def reset(self):
-        obs = self._next_out()[:self.M]
-        ops.mpe_world_comm_reset(self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep, self.episode, obs, self.N, self.seed, self.M)
-        return list(obs)
-
-    def step(self, actions):
-        mode, act = self._parse_actions(actions)
-        out = self._next_out()
-        obs, rew, dones = out[:self.M], out[self.M], out[self.M + 1]
-        ops.mpe_world_comm_step(self.agent_pos, self.agent_vel, self.landmark_pos, self.tstep, self.episode, act, mode, obs,
-                                rew.view(self.N, self.M), dones.view(torch.uint8), self.N, self.T, self.seed, self.M)
-        return list(obs), rew, dones, None

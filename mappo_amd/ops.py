@@ -28,6 +28,20 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _u64(x):
+    return int(x) & (2 ** 64 - 1)
+
+
+def _ptrs(tensors, dtypes):
+    """Pointers of an env's state tensors, in the order of its entry points, each with the dtype the kernels read it as."""
+    return [_ptr(t, d) for t, d in zip(tensors, dtypes, strict=True)]
+
+
+def _env_call(symbol, *args):
+    """An entry point that ends in the stream argument: call it on the current stream, check its return code under its name."""
+    _lib.check(getattr(_lib.load(), symbol)(*args, _stream()), symbol)
+
+
 def _ws(nbytes, device):
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
 
@@ -350,22 +364,27 @@ def rollout_episode(actor_params, actor_desc, critic_params, critic_desc, obs, r
     _lib.check(rc, "mappo_rollout_episode")
 
 
+# dtypes of the GPU-resident MPE envs' state tensors, in the order every entry point of a scenario takes them.  These rows guard
+# the ABI (include/mappo_hip.h); the envs' `state` descriptions (envs/mpe_*.py) state the same dtypes again to allocate with, and
+# a disagreement shows here as _ptr's TypeError at the first call
+_F64, _I32, _I64 = torch.float64, torch.int32, torch.int64
+_STATE_BODIES = (_F64, _F64, _F64, _I32, _I64)                  # agent_pos, agent_vel, landmark_pos, tstep, episode: spread, tag, world_comm
+_STATE_GOAL = (_F64, _F64, _F64, _I32, _I32, _I64)              # ... landmark_pos, goal, tstep, episode: reference, adversary, push
+_STATE_COMM = (_F64, _F64, _F64, _I32, _I32, _I32, _I64)        # listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode
+_STATE_CRYPTO = (_I32, _I32, _I32, _I32, _I64)                  # goal, key, comm, tstep, episode
+
+
 def rollout_episode_spread(actor_params, actor_desc, critic_params, critic_desc, T, N, M, L, env_episode_length, env_seed, agent_pos,
                            agent_vel, landmark_pos, tstep, episode, deterministic, seed, counter, counter_dev, obs_buf, share_buf,
                            rew_buf, mask_buf, actions, logp, values, next_values, centralized):
     """A whole rollout episode on the GPU-resident simple_spread env in one launch, env steps included
     (mappo_rollout_episode_spread): the five env state tensors (SimpleSpreadVecEnv) are read, stepped T times on the sampled
     actions and stored back; the buffer arrays are the contiguous SharedReplayBuffer tensors, as for rollout_episode."""
-    f64 = torch.float64
-    rc = _lib.load().mappo_rollout_episode_spread(_ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), int(T),
-                                                  int(N), int(M), int(L), int(env_episode_length), int(env_seed) & (2 ** 64 - 1),
-                                                  _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
-                                                  _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(bool(deterministic)),
-                                                  int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
-                                                  _ptr(counter_dev, torch.int64, allow_none=True), _ptr(obs_buf), _ptr(share_buf),
-                                                  _ptr(rew_buf), _ptr(mask_buf), _ptr(actions), _ptr(logp), _ptr(values), _ptr(next_values),
-                                                  int(bool(centralized)), _stream())
-    _lib.check(rc, "mappo_rollout_episode_spread")
+    _env_call("mappo_rollout_episode_spread", _ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), int(T),
+              int(N), int(M), int(L), int(env_episode_length), _u64(env_seed),
+              *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES), int(bool(deterministic)), _u64(seed),
+              _u64(counter), _ptr(counter_dev, _I64, allow_none=True),
+              *map(_ptr, (obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values, next_values)), int(bool(centralized)))
 
 
 def rollout_episode_spread_recurrent(actor_params, actor_desc, critic_params, critic_desc, T, N, M, L, env_episode_length, env_seed,
@@ -375,15 +394,12 @@ def rollout_episode_spread_recurrent(actor_params, actor_desc, critic_params, cr
     """The one-launch simple_spread episode of a recurrent shared policy (mappo_rollout_episode_spread_recurrent): as
     rollout_episode_spread, with the buffer's two rnn-state arrays [T+1, N, M, 1, 64] read at slot 0 and written at slots 1..T,
     and without the bootstrap value."""
-    f64 = torch.float64
-    rc = _lib.load().mappo_rollout_episode_spread_recurrent(
-        _ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), int(T), int(N), int(M), int(L),
-        int(env_episode_length), int(env_seed) & (2 ** 64 - 1), _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
-        _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(bool(deterministic)), int(seed) & (2 ** 64 - 1),
-        int(counter) & (2 ** 64 - 1), _ptr(counter_dev, torch.int64, allow_none=True), _ptr(obs_buf), _ptr(share_buf), _ptr(rew_buf),
-        _ptr(mask_buf), _ptr(actions), _ptr(logp), _ptr(values), _ptr(rnn_states), _ptr(rnn_states_critic), int(bool(centralized)),
-        _stream())
-    _lib.check(rc, "mappo_rollout_episode_spread_recurrent")
+    _env_call("mappo_rollout_episode_spread_recurrent", _ptr(actor_params), C.byref(actor_desc), _ptr(critic_params),
+              C.byref(critic_desc), int(T), int(N), int(M), int(L), int(env_episode_length), _u64(env_seed),
+              *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES), int(bool(deterministic)), _u64(seed),
+              _u64(counter), _ptr(counter_dev, _I64, allow_none=True),
+              *map(_ptr, (obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values, rnn_states, rnn_states_critic)),
+              int(bool(centralized)))
 
 
 def rollout_episode_reference(actor_params, actor_desc, critic_params, critic_desc, head_dims, T, N, env_episode_length, env_seed,
@@ -393,28 +409,24 @@ def rollout_episode_reference(actor_params, actor_desc, critic_params, critic_de
     (mappo_rollout_episode_reference): the six env state tensors (SimpleReferenceVecEnv) are read, stepped T times on the sampled
     head indices and stored back; the buffer arrays are the contiguous SharedReplayBuffer tensors (actions / action_log_probs
     [T, N, 2, 2]).  head_dims must be (5, 10)."""
-    f64 = torch.float64
     arr, K = _heads(head_dims)
-    rc = _lib.load().mappo_rollout_episode_reference(_ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), arr, K,
-                                                     int(T), int(N), int(env_episode_length), int(env_seed) & (2 ** 64 - 1),
-                                                     _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
-                                                     _ptr(goal, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64),
-                                                     int(bool(deterministic)), int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
-                                                     _ptr(counter_dev, torch.int64, allow_none=True), _ptr(obs_buf), _ptr(share_buf),
-                                                     _ptr(rew_buf), _ptr(mask_buf), _ptr(actions), _ptr(logp), _ptr(values), _ptr(next_values),
-                                                     int(bool(centralized)), _stream())
-    _lib.check(rc, "mappo_rollout_episode_reference")
+    _env_call("mappo_rollout_episode_reference", _ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), arr, K,
+              int(T), int(N), int(env_episode_length), _u64(env_seed),
+              *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL), int(bool(deterministic)), _u64(seed),
+              _u64(counter), _ptr(counter_dev, _I64, allow_none=True),
+              *map(_ptr, (obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values, next_values)), int(bool(centralized)))
 
 
+# ---- one rollout episode of the SEPARATED runner in one launch, env steps included (csrc/rollout_separated.h) ------------------------
 def comm_agent(actor_params, actor_desc, critic_params, critic_desc, seed, counter_dev, obs_buf, share_buf, rew_buf, mask_buf, actions, logp, values,
                next_values):
-    """One agent of rollout_episode_comm / rollout_episode_adversary (mappo_comm_agent): its networks, its sampling seed and counter word (int64 [1] device tensor or None) and the contiguous arrays of its
-    SeparatedReplayBuffer."""
+    """One agent of a separated one-launch episode (mappo_comm_agent; rollout_episode_comm and the five below it): its networks, its
+    sampling seed and counter word (int64 [1] device tensor or None) and the contiguous arrays of its SeparatedReplayBuffer."""
     ag = _lib.CommAgent()
     ag.actor_params, ag.critic_params = _ptr(actor_params).value, _ptr(critic_params).value
     ag.actor_desc, ag.critic_desc = actor_desc, critic_desc
-    ag.seed = int(seed) & (2 ** 64 - 1)
-    cd = _ptr(counter_dev, torch.int64, allow_none=True)
+    ag.seed = _u64(seed)
+    cd = _ptr(counter_dev, _I64, allow_none=True)
     ag.counter_dev = cd.value if cd is not None else None
     for name, t in (("obs_buf", obs_buf), ("share_buf", share_buf), ("rew_buf", rew_buf), ("mask_buf", mask_buf), ("actions", actions),
                     ("logp", logp), ("values", values), ("next_values", next_values)):
@@ -424,16 +436,12 @@ def comm_agent(actor_params, actor_desc, critic_params, critic_desc, seed, count
 
 def rollout_episode_comm(speaker, listener, T, N, env_episode_length, env_seed, listener_pos, listener_vel, landmark_pos, goal, symbol,
                          tstep, episode, deterministic, counter, centralized):
-    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_speaker_listener env in one launch, env steps
-    included (mappo_rollout_episode_comm).  speaker / listener: comm_agent(...) of agent 0 / 1; the seven env state tensors
-    (SimpleSpeakerListenerVecEnv) are read, stepped T times on the sampled indices and stored back."""
-    f64 = torch.float64
-    rc = _lib.load().mappo_rollout_episode_comm(C.byref(speaker), C.byref(listener), int(T), int(N), int(env_episode_length),
-                                                int(env_seed) & (2 ** 64 - 1), _ptr(listener_pos, f64), _ptr(listener_vel, f64),
-                                                _ptr(landmark_pos, f64), _ptr(goal, torch.int32), _ptr(symbol, torch.int32),
-                                                _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(bool(deterministic)),
-                                                int(counter) & (2 ** 64 - 1), int(bool(centralized)), _stream())
-    _lib.check(rc, "mappo_rollout_episode_comm")
+    """The episode on the GPU-resident simple_speaker_listener env (mappo_rollout_episode_comm).  speaker / listener: comm_agent(...)
+    of agent 0 / 1; the seven env state tensors (SimpleSpeakerListenerVecEnv) are read, stepped T times on the sampled indices and
+    stored back."""
+    _env_call("mappo_rollout_episode_comm", C.byref(speaker), C.byref(listener), int(T), int(N), int(env_episode_length), _u64(env_seed),
+              *_ptrs((listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode), _STATE_COMM), int(bool(deterministic)),
+              _u64(counter), int(bool(centralized)))
 
 
 def _episode_agents(who, scenario, M, agents):
@@ -445,76 +453,54 @@ def _episode_agents(who, scenario, M, agents):
 
 def rollout_episode_adversary(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
                               deterministic, counter, centralized):
-    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_adversary env in one launch, env steps included
-    (mappo_rollout_episode_adversary).  agents: the three comm_agent(...) of agents 0 (adversary), 1, 2 (good); the six env state
-    tensors (SimpleAdversaryVecEnv) are read, stepped T times on the sampled indices and stored back."""
-    f64 = torch.float64
+    """The episode on the GPU-resident simple_adversary env (mappo_rollout_episode_adversary).  agents: the three comm_agent(...) of
+    agents 0 (adversary), 1, 2 (good); the six env state tensors (SimpleAdversaryVecEnv) are read, stepped T times on the sampled
+    indices and stored back."""
     arr = _episode_agents("rollout_episode_adversary", "simple_adversary", 3, agents)
-    rc = _lib.load().mappo_rollout_episode_adversary(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
-                                                     _ptr(goal, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T),
-                                                     int(N), int(env_episode_length), int(env_seed) & (2 ** 64 - 1),
-                                                     int(bool(deterministic)), int(counter) & (2 ** 64 - 1), int(bool(centralized)),
-                                                     _stream())
-    _lib.check(rc, "mappo_rollout_episode_adversary")
+    _env_call("mappo_rollout_episode_adversary", arr, *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL),
+              int(T), int(N), int(env_episode_length), _u64(env_seed), int(bool(deterministic)), _u64(counter), int(bool(centralized)))
 
 
 def rollout_episode_tag(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, tstep, episode, deterministic,
                         counter, centralized):
-    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_tag env in one launch, env steps included
-    (mappo_rollout_episode_tag).  agents: the four comm_agent(...) of agents 0 .. 2 (adversaries) and 3 (good); the five env state
-    tensors (SimpleTagVecEnv) are read, stepped T times on the sampled indices and stored back."""
-    f64 = torch.float64
+    """The episode on the GPU-resident simple_tag env (mappo_rollout_episode_tag).  agents: the four comm_agent(...) of agents 0 .. 2
+    (adversaries) and 3 (good); the five env state tensors (SimpleTagVecEnv) are read, stepped T times on the sampled indices and
+    stored back."""
     arr = _episode_agents("rollout_episode_tag", "simple_tag", 4, agents)
-    rc = _lib.load().mappo_rollout_episode_tag(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
-                                               _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T), int(N), int(env_episode_length),
-                                               int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)), int(counter) & (2 ** 64 - 1),
-                                               int(bool(centralized)), _stream())
-    _lib.check(rc, "mappo_rollout_episode_tag")
+    _env_call("mappo_rollout_episode_tag", arr, *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES), int(T), int(N),
+              int(env_episode_length), _u64(env_seed), int(bool(deterministic)), _u64(counter), int(bool(centralized)))
 
 
 def rollout_episode_world_comm(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, tstep, episode, deterministic,
                                counter, centralized):
-    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_world_comm env in one launch, env steps included
-    (mappo_rollout_episode_world_comm) — the six ACTORS only: values / next_values are not written, the caller runs each critic
-    afterwards on share_obs.  agents: the six comm_agent(...) of agent 0 (the leader, whose actions / logp are [T, N, 2]), 1 .. 3
-    (adversaries) and 4, 5 (good); the five env state tensors (SimpleWorldCommVecEnv) are read, stepped T times on the sampled
-    indices and stored back."""
-    f64 = torch.float64
+    """The episode on the GPU-resident simple_world_comm env (mappo_rollout_episode_world_comm) — the six ACTORS only: values /
+    next_values are not written, the caller runs each critic afterwards on share_obs.  agents: the six comm_agent(...) of agent 0 (the
+    leader, whose actions / logp are [T, N, 2]), 1 .. 3 (adversaries) and 4, 5 (good); the five env state tensors
+    (SimpleWorldCommVecEnv) are read, stepped T times on the sampled indices and stored back."""
     arr = _episode_agents("rollout_episode_world_comm", "simple_world_comm", 6, agents)
-    rc = _lib.load().mappo_rollout_episode_world_comm(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
-                                                      _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T), int(N),
-                                                      int(env_episode_length), int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)),
-                                                      int(counter) & (2 ** 64 - 1), int(bool(centralized)), _stream())
-    _lib.check(rc, "mappo_rollout_episode_world_comm")
+    _env_call("mappo_rollout_episode_world_comm", arr, *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES), int(T),
+              int(N), int(env_episode_length), _u64(env_seed), int(bool(deterministic)), _u64(counter), int(bool(centralized)))
 
 
 def rollout_episode_push(agents, T, N, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, goal, tstep, episode,
                          deterministic, counter, centralized):
-    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_push env in one launch, env steps included
-    (mappo_rollout_episode_push).  agents: the two comm_agent(...) of agents 0 (adversary) and 1 (good); the six env state tensors
-    (SimplePushVecEnv) are read, stepped T times on the sampled indices and stored back."""
-    f64 = torch.float64
+    """The episode on the GPU-resident simple_push env (mappo_rollout_episode_push).  agents: the two comm_agent(...) of agents 0
+    (adversary) and 1 (good); the six env state tensors (SimplePushVecEnv) are read, stepped T times on the sampled indices and stored
+    back."""
     arr = _episode_agents("rollout_episode_push", "simple_push", 2, agents)
-    rc = _lib.load().mappo_rollout_episode_push(arr, _ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64),
-                                                _ptr(goal, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64), int(T),
-                                                int(N), int(env_episode_length), int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)),
-                                                int(counter) & (2 ** 64 - 1), int(bool(centralized)), _stream())
-    _lib.check(rc, "mappo_rollout_episode_push")
+    _env_call("mappo_rollout_episode_push", arr, *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL), int(T),
+              int(N), int(env_episode_length), _u64(env_seed), int(bool(deterministic)), _u64(counter), int(bool(centralized)))
 
 
 def rollout_episode_crypto(agents, T, N, env_episode_length, env_seed, goal, key, comm, tstep, episode, deterministic, counter,
                            centralized, num_landmarks=2):
-    """A whole rollout episode of the SEPARATED runner on the GPU-resident simple_crypto env in one launch, env steps included
-    (mappo_rollout_episode_crypto).  agents: the three comm_agent(...) of agents 0 (Eve), 1 (Bob) and 2 (Alice); the five env state
-    tensors (SimpleCryptoVecEnv) are read, stepped T times on the sampled symbols and stored back."""
-    i32 = torch.int32
+    """The episode on the GPU-resident simple_crypto env (mappo_rollout_episode_crypto).  agents: the three comm_agent(...) of agents 0
+    (Eve), 1 (Bob) and 2 (Alice); the five env state tensors (SimpleCryptoVecEnv) are read, stepped T times on the sampled symbols and
+    stored back."""
     arr = _episode_agents("rollout_episode_crypto", "simple_crypto", 3, agents)
     _crypto_shape("rollout_episode_crypto", 3, num_landmarks)
-    rc = _lib.load().mappo_rollout_episode_crypto(arr, _ptr(goal, i32), _ptr(key, i32), _ptr(comm, i32), _ptr(tstep, i32),
-                                                  _ptr(episode, torch.int64), int(T), int(N), int(num_landmarks), int(env_episode_length),
-                                                  int(env_seed) & (2 ** 64 - 1), int(bool(deterministic)), int(counter) & (2 ** 64 - 1),
-                                                  int(bool(centralized)), _stream())
-    _lib.check(rc, "mappo_rollout_episode_crypto")
+    _env_call("mappo_rollout_episode_crypto", arr, *_ptrs((goal, key, comm, tstep, episode), _STATE_CRYPTO), int(T), int(N),
+              int(num_landmarks), int(env_episode_length), _u64(env_seed), int(bool(deterministic)), _u64(counter), int(bool(centralized)))
 
 
 def mlp_backward_slabs(B):
@@ -876,88 +862,65 @@ def profile_arm(kernel, start_event, stop_event):
     _lib.check(rc, "mappo_profile_arm")
 
 
-# ---- GPU-vectorised MPE simple_spread (csrc/mpe_env.hip) -------------------------------------------------------------
+# ---- GPU-vectorised MPE envs: reset (state..., obs..., N, [shape...], seed) and step (state..., actions, mode, obs..., rewards, dones, N,
+# [shape...], episode_length, seed), one launch each ----
+# simple_spread (csrc/mpe_env.hip)
 def mpe_spread_reset(agent_pos, agent_vel, landmark_pos, tstep, episode, obs, N, M, L, seed):
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_spread_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
-                                            _ptr(episode, torch.int64), _ptr(obs),
-                                            int(N), int(M), int(L), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_spread_reset")
+    _env_call("mappo_mpe_spread_reset", *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES), _ptr(obs), int(N), int(M),
+              int(L), _u64(seed))
 
 
 def mpe_spread_step(agent_pos, agent_vel, landmark_pos, tstep, episode, actions, action_mode, obs, rewards, dones, N, M, L,
                     episode_length, seed):
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_spread_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
-                                           _ptr(episode, torch.int64), _ptr(actions), int(action_mode), _ptr(obs), _ptr(rewards),
-                                           _ptr(dones, torch.uint8), int(N), int(M), int(L),
-                                           int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_spread_step")
+    _env_call("mappo_mpe_spread_step", *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES), _ptr(actions),
+              int(action_mode), _ptr(obs), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(M), int(L), int(episode_length), _u64(seed))
 
 
-# ---- GPU-vectorised MPE simple_reference (csrc/mpe_ref_env.hip): 2 agents, 3 landmarks, MultiDiscrete (5, 10) ----------------
+# simple_reference (csrc/mpe_ref_env.hip): 2 agents, 3 landmarks, MultiDiscrete (5, 10)
 def mpe_reference_reset(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, obs, N, seed):
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_reference_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                               _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs), int(N),
-                                               int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_reference_reset")
+    _env_call("mappo_mpe_reference_reset", *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL), _ptr(obs), int(N),
+              _u64(seed))
 
 
 def mpe_reference_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, actions, action_mode, obs, rewards, dones, N,
                        episode_length, seed):
     """action_mode 0: actions [N, 2, 15] (the heads' one-hots side by side) | 1: [N, 2, 2] fp32 head indices."""
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_reference_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                              _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(actions), int(action_mode),
-                                              _ptr(obs), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length),
-                                              int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_reference_step")
+    _env_call("mappo_mpe_reference_step", *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL), _ptr(actions),
+              int(action_mode), _ptr(obs), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length), _u64(seed))
 
 
-# ---- GPU-vectorised MPE simple_speaker_listener (csrc/mpe_comm_env.hip): speaker Discrete(3), listener Discrete(5) -----------------
+# simple_speaker_listener (csrc/mpe_comm_env.hip): speaker Discrete(3), listener Discrete(5)
 def mpe_comm_reset(listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode, obs_speaker, obs_listener, N, seed):
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_comm_reset(_ptr(listener_pos, f64), _ptr(listener_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                          _ptr(symbol, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs_speaker),
-                                          _ptr(obs_listener), int(N), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_comm_reset")
+    _env_call("mappo_mpe_comm_reset", *_ptrs((listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode), _STATE_COMM),
+              _ptr(obs_speaker), _ptr(obs_listener), int(N), _u64(seed))
 
 
 def mpe_comm_step(listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode, actions_speaker, actions_listener, action_mode,
                   obs_speaker, obs_listener, rewards, dones, N, episode_length, seed):
     """action_mode 0: one-hots, actions_speaker [N, 3] and actions_listener [N, 5] | 1: actions_speaker = fp32 indices [N, 2]
     (symbol, move), actions_listener None."""
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_comm_step(_ptr(listener_pos, f64), _ptr(listener_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                         _ptr(symbol, torch.int32), _ptr(tstep, torch.int32), _ptr(episode, torch.int64),
-                                         _ptr(actions_speaker), _ptr(actions_listener, allow_none=True), int(action_mode), _ptr(obs_speaker),
-                                         _ptr(obs_listener), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length),
-                                         int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_comm_step")
+    _env_call("mappo_mpe_comm_step", *_ptrs((listener_pos, listener_vel, landmark_pos, goal, symbol, tstep, episode), _STATE_COMM),
+              _ptr(actions_speaker), _ptr(actions_listener, allow_none=True), int(action_mode), _ptr(obs_speaker), _ptr(obs_listener),
+              _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(episode_length), _u64(seed))
 
 
-# ---- GPU-vectorised MPE simple_adversary (csrc/mpe_adv_env.hip): adversary + two good agents, Discrete(5) each, per-agent rewards ------
+# The scenarios below pay every agent its OWN reward and share their kernels (csrc/mpe_ragged_env.hip over each scenario's
+# mpe_<scenario>_core.h): rewards [N, M], one per agent.
+# simple_adversary: adversary + two good agents, Discrete(5) each
 def mpe_adversary_reset(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, obs_adversary, obs_good1, obs_good2, N, seed, num_agents=3):
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_adversary_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                               _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs_adversary), _ptr(obs_good1),
-                                               _ptr(obs_good2), int(N), int(num_agents), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_adversary_reset")
+    _env_call("mappo_mpe_adversary_reset", *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL),
+              *map(_ptr, (obs_adversary, obs_good1, obs_good2)), int(N), int(num_agents), _u64(seed))
 
 
 def mpe_adversary_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, actions, action_mode, obs_adversary, obs_good1, obs_good2,
                        rewards, dones, N, episode_length, seed, num_agents=3):
-    """action_mode 0: one-hots [N, 3, 5] | 1: fp32 indices [N, 3].  rewards [N, 3]: one per agent."""
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_adversary_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                              _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(actions), int(action_mode),
-                                              _ptr(obs_adversary), _ptr(obs_good1), _ptr(obs_good2), _ptr(rewards), _ptr(dones, torch.uint8),
-                                              int(N), int(num_agents), int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_adversary_step")
+    """action_mode 0: one-hots [N, 3, 5] | 1: fp32 indices [N, 3]."""
+    _env_call("mappo_mpe_adversary_step", *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL), _ptr(actions),
+              int(action_mode), *map(_ptr, (obs_adversary, obs_good1, obs_good2, rewards)), _ptr(dones, torch.uint8), int(N), int(num_agents),
+              int(episode_length), _u64(seed))
 
 
-# ---- GPU-vectorised MPE simple_tag (csrc/mpe_tag_env.hip): three adversaries + one good agent, Discrete(5) each, per-agent rewards ------
+# simple_tag: three adversaries + one good agent, Discrete(5) each
 def _tag_agents(who, num_agents):
     if int(num_agents) != 4:
         raise ValueError(f"{who}: simple_tag is built for num_agents = 4: 3 adversaries, 1 good agent, 2 landmarks (got {num_agents})")
@@ -965,26 +928,20 @@ def _tag_agents(who, num_agents):
 
 def mpe_tag_reset(agent_pos, agent_vel, landmark_pos, tstep, episode, obs_adv0, obs_adv1, obs_adv2, obs_good, N, seed, num_agents=4):
     _tag_agents("mpe_tag_reset", num_agents)
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_tag_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
-                                         _ptr(episode, torch.int64), _ptr(obs_adv0), _ptr(obs_adv1), _ptr(obs_adv2), _ptr(obs_good), int(N),
-                                         int(num_agents), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_tag_reset")
+    _env_call("mappo_mpe_tag_reset", *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES),
+              *map(_ptr, (obs_adv0, obs_adv1, obs_adv2, obs_good)), int(N), int(num_agents), _u64(seed))
 
 
 def mpe_tag_step(agent_pos, agent_vel, landmark_pos, tstep, episode, actions, action_mode, obs_adv0, obs_adv1, obs_adv2, obs_good, rewards,
                  dones, N, episode_length, seed, num_agents=4):
-    """action_mode 0: one-hots [N, 4, 5] | 1: fp32 indices [N, 4].  rewards [N, 4]: one per agent."""
+    """action_mode 0: one-hots [N, 4, 5] | 1: fp32 indices [N, 4]."""
     _tag_agents("mpe_tag_step", num_agents)
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_tag_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
-                                        _ptr(episode, torch.int64), _ptr(actions), int(action_mode), _ptr(obs_adv0), _ptr(obs_adv1),
-                                        _ptr(obs_adv2), _ptr(obs_good), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(num_agents),
-                                        int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_tag_step")
+    _env_call("mappo_mpe_tag_step", *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES), _ptr(actions), int(action_mode),
+              *map(_ptr, (obs_adv0, obs_adv1, obs_adv2, obs_good, rewards)), _ptr(dones, torch.uint8), int(N), int(num_agents),
+              int(episode_length), _u64(seed))
 
 
-# ---- GPU-vectorised MPE simple_push (csrc/mpe_push_env.hip): one adversary + one good agent that collide, Discrete(5) each, per-agent rewards ------
+# simple_push: one adversary + one good agent that collide, Discrete(5) each
 def _push_agents(who, num_agents):
     if int(num_agents) != 2:
         raise ValueError(f"{who}: simple_push is built for num_agents = 2: 1 adversary, 1 good agent, 2 landmarks (got {num_agents})")
@@ -992,26 +949,20 @@ def _push_agents(who, num_agents):
 
 def mpe_push_reset(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, obs_adversary, obs_good, N, seed, num_agents=2):
     _push_agents("mpe_push_reset", num_agents)
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_push_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                          _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(obs_adversary), _ptr(obs_good), int(N),
-                                          int(num_agents), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_push_reset")
+    _env_call("mappo_mpe_push_reset", *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL), _ptr(obs_adversary),
+              _ptr(obs_good), int(N), int(num_agents), _u64(seed))
 
 
 def mpe_push_step(agent_pos, agent_vel, landmark_pos, goal, tstep, episode, actions, action_mode, obs_adversary, obs_good, rewards, dones, N,
                   episode_length, seed, num_agents=2):
-    """action_mode 0: one-hots [N, 2, 5] | 1: fp32 indices [N, 2].  rewards [N, 2]: one per agent."""
+    """action_mode 0: one-hots [N, 2, 5] | 1: fp32 indices [N, 2]."""
     _push_agents("mpe_push_step", num_agents)
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_push_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(goal, torch.int32),
-                                         _ptr(tstep, torch.int32), _ptr(episode, torch.int64), _ptr(actions), int(action_mode),
-                                         _ptr(obs_adversary), _ptr(obs_good), _ptr(rewards), _ptr(dones, torch.uint8), int(N),
-                                         int(num_agents), int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_push_step")
+    _env_call("mappo_mpe_push_step", *_ptrs((agent_pos, agent_vel, landmark_pos, goal, tstep, episode), _STATE_GOAL), _ptr(actions),
+              int(action_mode), _ptr(obs_adversary), _ptr(obs_good), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(num_agents),
+              int(episode_length), _u64(seed))
 
 
-# ---- GPU-vectorised MPE simple_crypto (csrc/mpe_crypto_env.hip): Eve, Bob and Alice only speak, Discrete(4) each, per-agent rewards ------
+# simple_crypto: Eve, Bob and Alice only speak, Discrete(4) each
 def _crypto_shape(who, num_agents, num_landmarks):
     if int(num_agents) != 3:
         raise ValueError(f"{who}: simple_crypto is built for num_agents = 3: adversary Eve, listener Bob, speaker Alice (got {num_agents})")
@@ -1022,27 +973,21 @@ def _crypto_shape(who, num_agents, num_landmarks):
 
 def mpe_crypto_reset(goal, key, comm, tstep, episode, obs_eve, obs_bob, obs_alice, N, seed, num_agents=3, num_landmarks=2):
     _crypto_shape("mpe_crypto_reset", num_agents, num_landmarks)
-    i32 = torch.int32
-    rc = _lib.load().mappo_mpe_crypto_reset(_ptr(goal, i32), _ptr(key, i32), _ptr(comm, i32), _ptr(tstep, i32), _ptr(episode, torch.int64),
-                                            _ptr(obs_eve), _ptr(obs_bob), _ptr(obs_alice), int(N), int(num_agents), int(num_landmarks),
-                                            int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_crypto_reset")
+    _env_call("mappo_mpe_crypto_reset", *_ptrs((goal, key, comm, tstep, episode), _STATE_CRYPTO), *map(_ptr, (obs_eve, obs_bob, obs_alice)),
+              int(N), int(num_agents), int(num_landmarks), _u64(seed))
 
 
 def mpe_crypto_step(goal, key, comm, tstep, episode, actions, action_mode, obs_eve, obs_bob, obs_alice, rewards, dones, N, episode_length,
                     seed, num_agents=3, num_landmarks=2):
-    """action_mode 0: one-hots [N, 3, 4] | 1: fp32 indices [N, 3].  rewards [N, 3]: one per agent."""
+    """action_mode 0: one-hots [N, 3, 4] | 1: fp32 indices [N, 3]."""
     _crypto_shape("mpe_crypto_step", num_agents, num_landmarks)
-    i32 = torch.int32
-    rc = _lib.load().mappo_mpe_crypto_step(_ptr(goal, i32), _ptr(key, i32), _ptr(comm, i32), _ptr(tstep, i32), _ptr(episode, torch.int64),
-                                           _ptr(actions), int(action_mode), _ptr(obs_eve), _ptr(obs_bob), _ptr(obs_alice), _ptr(rewards),
-                                           _ptr(dones, torch.uint8), int(N), int(num_agents), int(num_landmarks), int(episode_length),
-                                           int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_crypto_step")
+    _env_call("mappo_mpe_crypto_step", *_ptrs((goal, key, comm, tstep, episode), _STATE_CRYPTO), _ptr(actions), int(action_mode),
+              *map(_ptr, (obs_eve, obs_bob, obs_alice, rewards)), _ptr(dones, torch.uint8), int(N), int(num_agents), int(num_landmarks),
+              int(episode_length), _u64(seed))
 
 
-# ---- GPU-vectorised MPE simple_world_comm (csrc/mpe_world_comm_env.hip): four adversaries, the first a MultiDiscrete (5, 4) leader, +
-# two good agents, Discrete(5) each, per-agent rewards ------
+# simple_world_comm (its own kernels, csrc/mpe_world_comm_env.hip): four adversaries, the first a MultiDiscrete (5, 4) leader, + two
+# good agents, Discrete(5) each
 def _world_comm_shape(who, num_agents, num_adversaries, num_good_agents, num_landmarks):
     if (int(num_agents), int(num_adversaries), int(num_good_agents), int(num_landmarks)) != (6, 4, 2, 1):
         raise ValueError(f"{who}: simple_world_comm is built for num_agents = 6: 4 adversaries (the first their leader), 2 good agents, "
@@ -1062,28 +1007,22 @@ def mpe_world_comm_reset(agent_pos, agent_vel, landmark_pos, tstep, episode, obs
                          num_good_agents=2, num_landmarks=1):
     """obs: the six per-agent output tensors, [N, 34] x 4 then [N, 28] x 2."""
     _world_comm_shape("mpe_world_comm_reset", num_agents, num_adversaries, num_good_agents, num_landmarks)
-    f64 = torch.float64
-    rc = _lib.load().mappo_mpe_world_comm_reset(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
-                                                _ptr(episode, torch.int64), _ptr_array(list(obs), 6, "mpe_world_comm_reset: obs"),
-                                                int(N), int(num_agents), int(num_landmarks), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_world_comm_reset")
+    _env_call("mappo_mpe_world_comm_reset", *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES),
+              _ptr_array(list(obs), 6, "mpe_world_comm_reset: obs"), int(N), int(num_agents), int(num_landmarks), _u64(seed))
 
 
 def mpe_world_comm_step(agent_pos, agent_vel, landmark_pos, tstep, episode, actions, action_mode, obs, rewards, dones, N, episode_length, seed,
                         num_agents=6, num_adversaries=4, num_good_agents=2, num_landmarks=1):
     """action_mode 0: actions = the six one-hot tensors, [N, 9] of the leader (move | word) and [N, 5] x 5 | 1: actions = one tensor of
-    fp32 indices [N, 7]: leader move, leader word, agents 1..5.  obs as in mpe_world_comm_reset; rewards [N, 6]: one per agent."""
+    fp32 indices [N, 7]: leader move, leader word, agents 1..5.  obs as in mpe_world_comm_reset."""
     _world_comm_shape("mpe_world_comm_step", num_agents, num_adversaries, num_good_agents, num_landmarks)
-    f64 = torch.float64
     acts = list(actions) if int(action_mode) == 0 else [actions] + [None] * 5
     if acts[0] is None:
         raise ValueError("tensor required")
-    rc = _lib.load().mappo_mpe_world_comm_step(_ptr(agent_pos, f64), _ptr(agent_vel, f64), _ptr(landmark_pos, f64), _ptr(tstep, torch.int32),
-                                               _ptr(episode, torch.int64), _ptr_array(acts, 6, "mpe_world_comm_step: actions", allow_none=int(action_mode) != 0),
-                                               int(action_mode), _ptr_array(list(obs), 6, "mpe_world_comm_step: obs"),
-                                               _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(num_agents), int(num_landmarks),
-                                               int(episode_length), int(seed) & (2 ** 64 - 1), _stream())
-    _lib.check(rc, "mappo_mpe_world_comm_step")
+    _env_call("mappo_mpe_world_comm_step", *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES),
+              _ptr_array(acts, 6, "mpe_world_comm_step: actions", allow_none=int(action_mode) != 0), int(action_mode),
+              _ptr_array(list(obs), 6, "mpe_world_comm_step: obs"), _ptr(rewards), _ptr(dones, torch.uint8), int(N), int(num_agents),
+              int(num_landmarks), int(episode_length), _u64(seed))
 
 
 def synth_smac_pool(obs, share_obs, avail, rewards, dead, dones, p_death, p_term, seed, counter):

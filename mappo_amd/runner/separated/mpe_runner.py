@@ -8,15 +8,10 @@ use_centralized_V is the concatenation of all agents' observations of the thread
 Agents may differ in shape (MPE simple_speaker_listener: observations of 3 and 11 features, Discrete(3) and Discrete(5)): the env's
 observations are then a list of per-agent tensors (mappo_amd.envs.mpe_speaker_listener) or the reference's host form, an object
 array [N, M] of per-agent arrays; one-hot widths come from each agent's own action space.  On such an env feed-forward policies
-collect through mappo_rollout_step (one launch per agent for actor + critic), and on the GPU-resident speaker-listener env the
-whole episode — both agents' networks, the env steps and the inserts — is ONE launch (mappo_rollout_episode_comm) with the same
-buffer contents and env state, bit for bit; MAPPO_COMM_EPISODE=0 keeps the stepwise path (A/B runs, tests).  The GPU-resident
-simple_adversary env (three agents, observations of 8 / 10 / 10 features, per-agent rewards) runs the same two ways:
-mappo_rollout_episode_adversary, MAPPO_ADV_EPISODE=0 for the stepwise path.  The GPU-resident simple_tag env (four agents,
-observations of 16 / 16 / 16 / 14 features, per-agent rewards) likewise: mappo_rollout_episode_tag, MAPPO_TAG_EPISODE=0 for the
-stepwise path; and the GPU-resident simple_push env (two agents that collide, observations of 8 / 19 features, per-agent rewards):
-mappo_rollout_episode_push, MAPPO_PUSH_EPISODE=0; and the GPU-resident simple_crypto env (three agents that only speak, observations of
-4 / 8 / 8 features, per-agent rewards): mappo_rollout_episode_crypto, MAPPO_CRYPTO_EPISODE=0.  None of them is named below: the env brings `episode_launch` and `episode_flag`.
+collect through mappo_rollout_step (one launch per agent for actor + critic), and on a GPU-resident env of mappo_amd.envs.mpe_ragged
+(speaker_listener, adversary, tag, push, crypto) the whole episode — every agent's networks, the env steps and the inserts — is
+ONE launch with the same buffer contents and env state, bit for bit.  No scenario is named below: the env brings `episode_launch`,
+and `episode_flag`, the env variable that, set to 0, keeps the stepwise path (A/B runs, tests).
 
 One agent may be MultiDiscrete among Discrete ones where the env declares `accepts_multidiscrete_agents` (the GPU-resident
 simple_world_comm: its leader moves and speaks): that agent's buffer carries [T, N, K] actions and log-probs, `collect` keeps all K

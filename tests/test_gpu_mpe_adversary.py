@@ -1,4 +1,4 @@
-"""GPU-vectorised MPE simple_adversary: the env kernel (csrc/mpe_adv_env.hip) against the fixture stepped by the reference's own
+"""GPU-vectorised MPE simple_adversary: the env kernel (csrc/mpe_ragged_env.hip) against the fixture stepped by the reference's own
 environment (tests/golden/mpe_adversary.npz) — outputs EQUAL the fp32 cast —, its reset against the host Philox, the one-launch
 episode (mappo_rollout_episode_adversary) bit for bit against the stepwise path, sampling against float64 and the host Philox, and
 the separated runner on three agents of two observation widths and per-agent rewards."""

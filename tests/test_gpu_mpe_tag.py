@@ -1,4 +1,4 @@
-"""GPU-vectorised MPE simple_tag: the env kernel (csrc/mpe_tag_env.hip) against the fixture stepped by the reference's own
+"""GPU-vectorised MPE simple_tag: the env kernel (csrc/mpe_ragged_env.hip) against the fixture stepped by the reference's own
 environment (tests/golden/mpe_tag.npz) — outputs within 1e-6 of the fp32 cast, the float64 state against the NumPy mirror —, its
 reset against the host Philox, and the separated runner's stepwise path on four agents of two observation widths and per-agent
 rewards."""
