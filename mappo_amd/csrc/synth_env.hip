@@ -25,9 +25,15 @@ struct SynthArgs {
 __device__ __forceinline__ float synth_uniform(uint64_t seed, uint64_t ctr, uint64_t idx) {       // (0, 1]
   return ((float)(philox_u32(seed, ctr, idx) >> 8) + 1.0f) * (1.0f / 16777216.0f);
 }
-__device__ __forceinline__ float synth_normal(uint64_t seed, uint64_t ctr, uint64_t idx) {        // Box-Muller
-  const float u1 = synth_uniform(seed, ctr, 2 * idx), u2 = synth_uniform(seed, ctr, 2 * idx + 1);
-  return sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530718f * u2);
+// Box-Muller in float64, rounded to float once.  The uniforms sit on a 24-bit grid, and in float32 the formula cannot tell two
+// neighbours of that grid apart: the product 6.2831853f * u2 alone rounds by up to 2.4e-7 where one step of u2 turns the angle by
+// 3.7e-7 (measured against float64, in units of the change one grid step makes: up to 2.6 with NumPy's float32, 3.2 with the
+// __logf / __cosf this function used before, 0.62 now — a correctly rounded float32; tests/test_gpu_synth_env.py).
+// cospi takes the angle in half turns, so its argument is exact.  About 100 float64 operations per normal on top of the two Philox
+// words: the step launch of the c4 shape went from 27 to 35 us, a pooled step from 18 to 31 us.
+__device__ __forceinline__ float synth_normal(uint64_t seed, uint64_t ctr, uint64_t idx) {
+  const double u1 = (double)synth_uniform(seed, ctr, 2 * idx), u2 = (double)synth_uniform(seed, ctr, 2 * idx + 1);
+  return (float)(sqrt(-2.0 * log(u1)) * cospi(2.0 * u2));
 }
 
 __global__ __launch_bounds__(256) void synth_smac_step_kernel(SynthArgs p) {
