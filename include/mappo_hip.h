@@ -566,6 +566,31 @@ int mappo_rollout_episode_spread_recurrent(const float *actor_params, const mapp
                                            float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/, float *values /*[T][B]*/,
                                            float *rnn_states /*[T+1][B][64]*/, float *rnn_states_critic /*[T+1][B][64]*/,
                                            int32_t centralized, mappo_stream_t stream);
+/* One launch per rollout EPISODE of a RECURRENT shared policy on SMAC-shaped env output (csrc/rollout_smac_rec.h;
+ * smac_runner.py:110-151 collect / insert over a whole episode): what mappo_recurrent_step_dual on slot 0, then for k = 1 .. T-1
+ * mappo_recurrent_rollout_step (insert of env output k - 1 into slot k + the step on it), then mappo_insert_smac of env output T - 1
+ * into slot T do, bit for bit while the stepwise step is the fused one (N*M <= 1024 rows).  The env output of all T steps is an
+ * input (the pool of mappo_synth_smac_pool: an env that ignores the actions): env_obs [T][N*M][D], env_share_obs [T][N*M][S],
+ * env_avail [T][N*M][A] or NULL (then avail_buf is NULL too), env_rewards [T][N] (shared by an env's agents), env_dones [T][N*M]
+ * bool bytes, env_bad_transition [N*M] bool bytes or NULL (constant over the episode).  Per step k < T: actor and critic (trunk,
+ * GRU step on rnn_states[k] * mask_buf[k], rnn.norm, head) on the rows of slot k -> actions / logp / values [T][B], B = N*M, the
+ * actor's logits masked by available_actions[k] (-1e10), sampling with counter + k (+ *counter_dev) and the buffer row; then
+ * env output k -> slot k + 1 of obs_buf / share_buf / avail_buf ([T+1][B][D | S | A]), rewards -> rew_buf [T][B] slot k,
+ * mask_buf[k+1] = 1 - dones_env (all agents of the env done), active_mask_buf[k+1] = dones_env ? 1 : 1 - done, bad_mask_buf[k+1] =
+ * 1 - bad_transition (all [T+1][B]), next states * (1 - dones_env) -> rnn_states / rnn_states_critic [T+1][B][64] slot k + 1
+ * (smac_runner.py:129-151).  centralized 0: the critic reads obs (in_dim = the actor's) and share_buf receives obs; env_share_obs
+ * is ignored.  The bootstrap value of slot T is NOT computed (the caller takes it, as the stepwise path does).
+ * Limits, each refused with a message that names it: both descriptors recurrent; both in_dim <= 64 (wider inputs step one launch at
+ * a time); layer_N <= 1; same layer_N and activation; actor out_dim <= MAPPO_MAX_ACTIONS; critic out_dim 1; 1 <= M <= 16; T >= 1;
+ * no NULL among the required arrays.  Validates on the host before the launch. */
+int mappo_rollout_episode_smac_recurrent(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, const float *critic_params,
+                                         const mappo_net_desc *critic_desc /*host*/, int32_t T, int32_t N, int32_t M, const float *env_obs,
+                                         const float *env_share_obs, const float *env_avail /*or NULL*/, const float *env_rewards,
+                                         const uint8_t *env_dones, const uint8_t *env_bad_transition /*or NULL*/, int32_t deterministic,
+                                         uint64_t seed, uint64_t counter, const uint64_t *counter_dev, float *obs_buf, float *share_buf,
+                                         float *avail_buf /*or NULL*/, float *rew_buf, float *mask_buf, float *bad_mask_buf,
+                                         float *active_mask_buf, float *rnn_states, float *rnn_states_critic, float *actions /*[T][B]*/,
+                                         float *logp /*[T][B]*/, float *values /*[T][B]*/, int32_t centralized, mappo_stream_t stream);
 
 /* GPU-vectorised MPE simple_reference (csrc/mpe_ref_env.hip, device functions in csrc/mpe_ref_core.h): N environments of
  * the scenario's fixed shape — 2 agents, 3 landmarks, dim_c = 10, action space MultiDiscrete([[0, 4], [0, 9]]) — one launch per step.

@@ -279,6 +279,39 @@ class R_MAPPOPolicy:
                                              b.masks, b.actions, b.action_log_probs, b.value_preds, b.rnn_states, b.rnn_states_critic,
                                              centralized)
 
+    def smac_episode_layout_ok(self, buffer, device):
+        """What mappo_rollout_episode_smac_recurrent reads and writes in place: contiguous fp32 buffer tensors on `device`,
+        recurrent_N = 1, hidden_size 64, at most 16 agents (a 16-row tile holds whole environments)."""
+        b = buffer
+        arrs = [b.obs, b.share_obs, b.rewards, b.masks, b.bad_masks, b.active_masks, b.actions, b.action_log_probs, b.value_preds,
+                b.rnn_states, b.rnn_states_critic] + ([b.available_actions] if b.available_actions is not None else [])
+        return (all(t.is_contiguous() and t.dtype == torch.float32 and t.device == device for t in arrs) and b.recurrent_N == 1
+                and b.rnn_states.shape[-1] == 64 and 1 <= b.num_agents <= 16 and b.actions.shape[-1] == 1)
+
+    @torch.no_grad()
+    def collect_episode_smac_fused_recurrent(self, buffer, block, centralized=True, deterministic=False):
+        """A whole rollout episode of a recurrent policy on SMAC-shaped env output in one launch
+        (mappo_rollout_episode_smac_recurrent): `block` = SyntheticSMACEnv.episode_block(), the env output of all T steps.  Writes
+        what collect_into on slot 0, T - 1 x collect_step_fused_recurrent and the last insert write — buffer.{actions,
+        action_log_probs, value_preds, rewards}[0..T-1], obs / share_obs / available_actions / masks / bad_masks / active_masks /
+        rnn_states / rnn_states_critic [1..T].  The bootstrap value is the caller's (compute()).  Step k samples with counter
+        k + *_counter_dev, as the stepwise path does."""
+        obs, share_obs, rewards, dones, bad, avail = block
+        b = buffer
+        T, N, M = b.episode_length, b.n_rollout_threads, b.num_agents
+        if tuple(obs.shape[:3]) != (T, N, M) or obs.device != b.device:
+            raise ValueError("collect_episode_smac_fused_recurrent: the env's block does not match the buffer (steps / threads / agents / device)")
+        if not self.smac_episode_layout_ok(b, obs.device):
+            raise ValueError("collect_episode_smac_fused_recurrent: the buffer does not have the device layout "
+                             "mappo_rollout_episode_smac_recurrent writes")
+        if b.available_actions is None:
+            avail = None
+        ops.rollout_episode_smac_recurrent(self.actor.flat, self.actor.desc, self.critic.flat, self.critic.desc, obs,
+                                           share_obs if centralized else None, avail, rewards, dones, bad, deterministic, self.actor._seed, 0,
+                                           self.actor._counter_dev, b.obs, b.share_obs, b.available_actions if avail is not None else None,
+                                           b.rewards, b.masks, b.bad_masks, b.active_masks, b.rnn_states, b.rnn_states_critic, b.actions,
+                                           b.action_log_probs, b.value_preds, centralized)
+
     def can_fuse_episode_reference(self):
         """mappo_rollout_episode_reference: the MultiDiscrete (5, 10) policy of MPE simple_reference — 21 observation features, a
         critic on 42 (centralized) or 21, what the stepwise MultiDiscrete launch covers (narrow, layer_N <= 1, not recurrent)."""

@@ -135,6 +135,8 @@ __device__ __forceinline__ void gru_step3_load(Step3W<TLN> &W, const GruFwdArgs 
 // TR 3: the tile's trunk features arrive through LDS, xs[b][lane] = features 16 b + 4 q .. + 3 of row n (written by the wave that
 // ran the trunk of a wide-input network in the same workgroup, behind a barrier: mlp_wide16.h, wide_recurrent_step_dual_kernel)
 // TR 4 | 5: one step of the one-launch recurrent episode (rollout_spread_rec.h; fused ReLU | tanh trunk with its weights in LDS).
+// TR 6 | 7: the same step for the SMAC-shaped episode (rollout_smac_rec.h): up to MAPPO_MAX_ACTIONS actions, and the sampling lanes
+// take the row's available_actions from ep->avail (the tile's [16][A] rows of the step, or NULL).
 // The workgroup holds TWO networks of four waves each, which come through here side by side (every barrier below is passed by
 // both; each has its own Step3Shared); `ep` (Step3Ep) names the tile: input rows, previous state and masks in LDS, buffer rows
 // ep->row0 .. + ep->R - 1 of slot offset ep->so, sampling counter ep->ctr.  The new state goes to the next step's LDS tile and
@@ -150,12 +152,12 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
   if constexpr (TR >= 4) so = ep->so;
   const int64_t B = p.Nc;                                       // L == 1: column = sequence
   const int A = p.A;
-  if constexpr (TR >= 4) __builtin_assume(A <= 16);             // (the episode's entry point takes 5 actions: no second head block)
+  if constexpr (TR == 4 || TR == 5) __builtin_assume(A <= 16);  // (the spread episode's entry point takes 5 actions: no second head block)
   const int u0 = 16 * w + 4 * q;
   const g4_t (&wi)[3][4] = W.wi, (&wh)[3][4] = W.wh;
   const Trunk16R<TLN> &tw = W.tw;
-  const g4_t bir = W.bir, biz = W.biz, bin = W.bin, bhr = W.bhr, bhz = W.bhz, bhn = W.bhn, nw4 = W.nw4, nb4 = W.nb4;
-  const g4_t hw[2] = {W.hw[0], W.hw[1]};
+  g4_t bir = W.bir, biz = W.biz, bin = W.bin, bhr = W.bhr, bhz = W.bhz, bhn = W.bhn, nw4 = W.nw4, nb4 = W.nb4;
+  g4_t hw[2] = {W.hw[0], W.hw[1]};                              // (assigned again only by TR 6 | 7, behind the trunk)
   for (int tile = bid; tile < n_tiles; tile += nb) {
     int c = tile * 16 + n;
     bool ok = c < p.Nc;
@@ -174,7 +176,11 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
       mk = ok ? p.masks[p.rows ? (int64_t)p.rows[cc] : (int64_t)cc] : 0.f;
     }
     uint32_t dead = 0u;
-    if (HM == 2 && p.avail && w == 0 && q == 0) dead = avail_dead_mask(p.avail + (int64_t)cc * A, A);    // the sampling lanes
+    if constexpr (TR >= 6) {
+      if (HM == 2 && ep->avail && w == 0 && q == 0) dead = avail_dead_mask(ep->avail + (ok ? n : 0) * A, A);
+    } else {
+      if (HM == 2 && p.avail && w == 0 && q == 0) dead = avail_dead_mask(p.avail + (int64_t)cc * A, A);    // the sampling lanes
+    }
     g4_t x[4], hm[4];
     if constexpr (TR == 3) {
 #pragma unroll
@@ -190,8 +196,10 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
       for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) xin[b][i] = ep->xrow[min(16 * b + 4 * q + i, D - 1)];
-      trunk16r_apply<TR == 4, TLN>(ep->tw, xin, x, D, ok, p.desc.use_feature_norm != 0, q);
+      trunk16r_apply<TR == 4 || TR == 6, TLN>(ep->tw, xin, x, D, ok, p.desc.use_feature_norm != 0, q);
       ep->late();                                               // a wave whose GRU slices (W.wi / W.wh) wait in LDS takes them now
+      // the SMAC episode's waves take their biases, rnn.norm vectors and head rows from LDS here, behind the trunk (W is not written)
+      if constexpr (TR >= 6) ep->fill(bir, biz, bin, bhr, bhz, bhn, nw4, nb4, hw);
 #pragma unroll
       for (int b = 0; b < 4; ++b) hm[b] = *reinterpret_cast<const g4_t *>(ep->hs + n * ep->hs_stride + 16 * b + 4 * q);
     } else if constexpr (TR != 0) {

@@ -152,5 +152,27 @@ class SyntheticSMACEnv:
         bad = torch.zeros(N, M, dtype=torch.bool, device=dev)
         return obs, share, rewards, dones, bad, avail
 
+    def episode_block(self):
+        """The env output of the next `pool_steps` steps at once (the runner's one-launch episode,
+        mappo_rollout_episode_smac_recurrent): the pool step() would hand out step by step, drawn by the same launch with the same
+        counter advance, and `_t` advanced by P.  Returns (obs [P, N, M, D], share_obs [P, N, M, S], rewards [P, N] — shared by an
+        env's agents —, dones [P, N, M] bool, bad_transition [N, M] bool, avail [P, N, M, A]); views, valid until the next pool.
+        Needs a device env with pool_steps > 0 and a pool-aligned `_t`."""
+        N, M, dev, P = self.N, self.M, self.device, self.pool_steps
+        if dev.type != "cuda" or P <= 0:
+            raise RuntimeError("SyntheticSMACEnv.episode_block: needs a device env (device='cuda') with pool_steps > 0; "
+                               f"got device={dev.type!r}, pool_steps={P}")
+        assert self._t % P == 0, "episode_block: _t must be at a pool boundary"
+        from mappo_amd import ops
+        if not hasattr(self, "_pool"):                      # (the arrays step() allocates)
+            self._pool = dict(obs=torch.empty(P, N, M, self.D, device=dev), share=torch.empty(P, N, M, self.S, device=dev),
+                              avail=torch.empty(P, N, M, self.A, device=dev), rew=torch.empty(P, N, device=dev),
+                              dones=torch.zeros(P, N, M, dtype=torch.bool, device=dev), bad=torch.zeros(N, M, dtype=torch.bool, device=dev),
+                              ctr=torch.tensor([1] + [0] * 33, dtype=torch.int64, device=dev))
+        q = self._pool
+        ops.synth_smac_pool(q["obs"], q["share"], q["avail"], q["rew"], self.dead, q["dones"], self.p_death, self.p_term, self.seed, q["ctr"])
+        self._t += P
+        return q["obs"], q["share"], q["rew"], q["dones"], q["bad"], q["avail"]
+
     def close(self):
         pass

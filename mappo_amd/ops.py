@@ -402,6 +402,30 @@ def rollout_episode_spread_recurrent(actor_params, actor_desc, critic_params, cr
               int(bool(centralized)))
 
 
+def rollout_episode_smac_recurrent(actor_params, actor_desc, critic_params, critic_desc, env_obs, env_share_obs, env_avail, env_rewards,
+                                   env_dones, env_bad, deterministic, seed, counter, counter_dev, obs_buf, share_buf, avail_buf, rew_buf,
+                                   mask_buf, bad_mask_buf, active_mask_buf, rnn_states, rnn_states_critic, actions, logp, values, centralized):
+    """The one-launch episode of a recurrent shared policy on SMAC-shaped env output (mappo_rollout_episode_smac_recurrent).  env_*:
+    the env output of all T steps, contiguous — obs [T, N, M, D], share_obs [T, N, M, S] (None when not centralized), avail
+    [T, N, M, A] or None, rewards [T, N], dones [T, N, M] bool, bad [N, M] bool or None; the buffer arrays are the contiguous
+    SharedReplayBuffer tensors (available_actions None together with env_avail).  A limit the kernel refuses (a wide observation,
+    layer_N 2, a feed-forward descriptor, more than 16 agents, ...) raises ValueError with the library's message."""
+    if env_obs.dim() != 4 or tuple(env_dones.shape) != tuple(env_obs.shape[:3]) or tuple(env_rewards.shape) != tuple(env_obs.shape[:2]):
+        raise ValueError(f"rollout_episode_smac_recurrent: env output shapes obs {tuple(env_obs.shape)} / rewards {tuple(env_rewards.shape)} / "
+                         f"dones {tuple(env_dones.shape)} are not [T, N, M, D] / [T, N] / [T, N, M]")
+    T, N, M, _ = env_obs.shape
+    n = lambda t, dtype=torch.float32: _ptr(t, dtype, allow_none=True)
+    rc = _lib.load().mappo_rollout_episode_smac_recurrent(
+        _ptr(actor_params), C.byref(actor_desc), _ptr(critic_params), C.byref(critic_desc), int(T), int(N), int(M), _ptr(env_obs),
+        n(env_share_obs), n(env_avail), _ptr(env_rewards), _ptr(env_dones, torch.bool), n(env_bad, torch.bool), int(bool(deterministic)),
+        _u64(seed), _u64(counter), n(counter_dev, _I64), _ptr(obs_buf), _ptr(share_buf), n(avail_buf), _ptr(rew_buf), _ptr(mask_buf),
+        _ptr(bad_mask_buf), _ptr(active_mask_buf), _ptr(rnn_states), _ptr(rnn_states_critic), _ptr(actions), _ptr(logp), _ptr(values),
+        int(bool(centralized)), _stream())
+    if rc == -1:                                       # MAPPO_EINVAL: refused on the host, nothing was launched
+        raise ValueError(_lib.load().mappo_last_error().decode("utf-8", "replace"))
+    _lib.check(rc, "mappo_rollout_episode_smac_recurrent")
+
+
 def rollout_episode_reference(actor_params, actor_desc, critic_params, critic_desc, head_dims, T, N, env_episode_length, env_seed,
                               agent_pos, agent_vel, landmark_pos, goal, tstep, episode, deterministic, seed, counter, counter_dev, obs_buf,
                               share_buf, rew_buf, mask_buf, actions, logp, values, next_values, centralized):

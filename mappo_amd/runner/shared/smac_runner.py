@@ -4,6 +4,7 @@ log_train, eval).  SMAC-style vec-env contract (env_wrappers.py:363-379): `reset
 `infos[i][m]['bad_transition']`.  The rollout step is fused like MPERunner's: the policy kernels write actions /
 log-probs / values into buffer slot `step`, `insert` stores what the environment returned and derives masks,
 active_masks and bad_masks exactly as smac_runner.py:129-151."""
+import os
 import time
 from functools import reduce
 
@@ -69,6 +70,16 @@ class SMACRunner(Runner):
         infos = None
         pol, b = self.trainer.policy, self.buffer
         pol.actor._counter_dev.add_(self.episode_length)   # fresh sampling stream per (replayed) episode
+        if self._episode_launch_ok():
+            # opt-in: the env hands out the whole episode's output at once (it ignores the actions) and the policy is recurrent with
+            # narrow inputs — steps 0 .. T-1 (both networks' GRU steps, every SMAC insert) are ONE launch
+            # (mappo_rollout_episode_smac_recurrent), same buffer contents and env state as the stepwise loop below; the bootstrap
+            # value stays compute()'s
+            self.trainer.prep_rollout()
+            pol.collect_episode_smac_fused_recurrent(b, self.envs.episode_block(), self.use_centralized_V)
+            b.step = 0
+            self.compute()
+            return infos
         # device envs + recurrent policies: the insert of step k - 1's env output rides in step k's launch (mappo_recurrent_rollout_step)
         fuse = (self._fuse_insert and env_takes_device_actions(self.envs)
                 and pol.can_fuse_recurrent_step(b.n_rollout_threads * b.num_agents))
@@ -97,6 +108,24 @@ class SMACRunner(Runner):
             self._insert_pending(pending)                       # the last env output: slot T (read by compute())
         self.compute()
         return infos
+
+    def _episode_launch_ok(self):
+        """The one-launch episode (MAPPO_SMAC_REC_EPISODE=1): an env with episode_block() whose pool is one episode long and stands at
+        an episode boundary, a policy within mappo_rollout_episode_smac_recurrent's limits (both networks recurrent, inputs <= 64,
+        layer_N <= 1, one Categorical head), the buffer contiguous fp32 on the env's device with the env's shapes."""
+        if os.environ.get("MAPPO_SMAC_REC_EPISODE", "0") != "1":
+            return False
+        env, pol, b, T = self.envs, self.trainer.policy, self.buffer, self.episode_length
+        if not (hasattr(env, "episode_block") and getattr(env, "pool_steps", 0) == T and getattr(env, "_t", 1) % T == 0):
+            return False
+        if not (env_takes_device_actions(env) and pol.can_fuse_episode_recurrent()):
+            return False
+        dev = torch.device(getattr(env, "device", "cpu"))
+        if dev.type != "cuda" or b.available_actions is None or not pol.smac_episode_layout_ok(b, b.device) or dev != b.device:
+            return False
+        D, S, A = b.obs.shape[-1], b.share_obs.shape[-1], b.available_actions.shape[-1]
+        return ((env.N, env.M, env.D, env.A) == (b.n_rollout_threads, b.num_agents, D, A) and pol.actor.desc.in_dim == D
+                and pol.critic.desc.in_dim == S and S == (env.S if self.use_centralized_V else D) and b.step == 0)
 
     def _insert_pending(self, pending):
         obs, share_obs, rewards, dones, infos, available_actions, rnn_states, rnn_states_critic = pending
