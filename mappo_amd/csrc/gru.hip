@@ -247,11 +247,11 @@ __global__ __launch_bounds__(256, 1) void gru_fwd_kernel(GruFwdArgs p) {
 }
 
 // the same with the SMAC insert of the env output the rows are read from as a third workgroup role (mappo_recurrent_rollout_step)
-template <int TR, int TLN>
+template <bool RELU, int TLN>
 __global__ __launch_bounds__(256, 1) void gru_step3f_dual_ins_kernel(GruFwdArgs a, GruFwdArgs c, int nA, SmacInsert ins, int nI) {
   __shared__ Step3Shared sh;
-  if ((int)blockIdx.x < nA) gru_step3_body<2, TR, TLN>(a, sh, blockIdx.x, nA);
-  else if ((int)blockIdx.x < 2 * nA) gru_step3_body<1, TR, TLN>(c, sh, blockIdx.x - nA, nA);
+  if ((int)blockIdx.x < nA) gru_step3_body<2, Step3Src::Fused, RELU, TLN>(a, sh, blockIdx.x, nA);
+  else if ((int)blockIdx.x < 2 * nA) gru_step3_body<1, Step3Src::Fused, RELU, TLN>(c, sh, blockIdx.x - nA, nA);
   else insert_smac_body(ins, (int)blockIdx.x - 2 * nA, nI);
 }
 
@@ -268,11 +268,11 @@ __global__ __launch_bounds__(256, 1) void gru_step3_dual_kernel(GruFwdArgs a, Gr
 }
 
 // trunk + GRU step + head of a recurrent actor AND critic (narrow inputs) in ONE launch
-template <int TR, int TLN>
+template <bool RELU, int TLN>
 __global__ __launch_bounds__(256, 1) void gru_step3f_dual_kernel(GruFwdArgs a, GruFwdArgs c, int nA) {
   __shared__ Step3Shared sh;
-  if ((int)blockIdx.x < nA) gru_step3_body<2, TR, TLN>(a, sh, blockIdx.x, nA);
-  else gru_step3_body<1, TR, TLN>(c, sh, blockIdx.x - nA, gridDim.x - nA);
+  if ((int)blockIdx.x < nA) gru_step3_body<2, Step3Src::Fused, RELU, TLN>(a, sh, blockIdx.x, nA);
+  else gru_step3_body<1, Step3Src::Fused, RELU, TLN>(c, sh, blockIdx.x - nA, gridDim.x - nA);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------
@@ -407,8 +407,8 @@ extern "C" int mappo_recurrent_step_dual(const float *actor_params, const mappo_
   hipStream_t st = as_stream(stream);
   const bool relu = actor_desc->use_relu != 0;
   switch (actor_desc->layer_N) {
-    case 0: if (relu) hipLaunchKernelGGL((gru_step3f_dual_kernel<1, 0>), grid, block, 0, st, a, c, g3); else hipLaunchKernelGGL((gru_step3f_dual_kernel<2, 0>), grid, block, 0, st, a, c, g3); break;
-    default: if (relu) hipLaunchKernelGGL((gru_step3f_dual_kernel<1, 1>), grid, block, 0, st, a, c, g3); else hipLaunchKernelGGL((gru_step3f_dual_kernel<2, 1>), grid, block, 0, st, a, c, g3); break;
+    case 0: if (relu) hipLaunchKernelGGL((gru_step3f_dual_kernel<true, 0>), grid, block, 0, st, a, c, g3); else hipLaunchKernelGGL((gru_step3f_dual_kernel<false, 0>), grid, block, 0, st, a, c, g3); break;
+    default: if (relu) hipLaunchKernelGGL((gru_step3f_dual_kernel<true, 1>), grid, block, 0, st, a, c, g3); else hipLaunchKernelGGL((gru_step3f_dual_kernel<false, 1>), grid, block, 0, st, a, c, g3); break;
   }
   MAPPO_CHECK_LAUNCH("recurrent_step_dual");
   return MAPPO_OK;
@@ -470,8 +470,8 @@ extern "C" int mappo_recurrent_rollout_step(const float *actor_params, const map
   hipStream_t st = as_stream(stream);
   const bool relu = actor_desc->use_relu != 0;
   switch (actor_desc->layer_N) {
-    case 0: if (relu) hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<1, 0>), grid, block, 0, st, a, c, g3, ins, nI); else hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<2, 0>), grid, block, 0, st, a, c, g3, ins, nI); break;
-    default: if (relu) hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<1, 1>), grid, block, 0, st, a, c, g3, ins, nI); else hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<2, 1>), grid, block, 0, st, a, c, g3, ins, nI); break;
+    case 0: if (relu) hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<true, 0>), grid, block, 0, st, a, c, g3, ins, nI); else hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<false, 0>), grid, block, 0, st, a, c, g3, ins, nI); break;
+    default: if (relu) hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<true, 1>), grid, block, 0, st, a, c, g3, ins, nI); else hipLaunchKernelGGL((gru_step3f_dual_ins_kernel<false, 1>), grid, block, 0, st, a, c, g3, ins, nI); break;
   }
   MAPPO_CHECK_LAUNCH("recurrent_rollout_step");
   return MAPPO_OK;

@@ -27,8 +27,6 @@ __host__ __device__ inline GruLds gru_lds(int n_waves, int wave_rows, bool with_
   m.total = p;
   return m;
 }
-__host__ __device__ inline int al4(int p);
-
 
 // Gate nonlinearities on the hardware transcendental units (v_exp_f32 / v_rcp_f32, 1 ulp each): ~5 instructions instead of
 // the ~30 (sigmoid) / ~50 (tanh) of the libm forms — per step and lane the recurrences evaluate 32 + 16 of them back to
@@ -95,10 +93,14 @@ __device__ __forceinline__ g4_t g4_load(const float *p) { const g4u_t v = *reint
 __device__ __forceinline__ g4_t mfma16g(float a, float b, g4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float quad_sum16g(float v) { return xhalf_sum(xrow_sum(v)); }     // lanes n, n + 16, n + 32, n + 48
 
-// TR: 0 = trunk features from xT | 1 = fused, ReLU trunk | 2 = fused, tanh trunk;  TLN: the trunk's layer_N (fused only).
-// Fused: every wave of the workgroup runs the (narrow-input) trunk of the tile itself with the weights in registers
-// (mlp_trunk16r.h) — the trunk's output in the accumulator layout IS the B operand of the W_ih products, so there is nothing to
-// exchange — and the separate features launch (a ~10 us floor per step) disappears.
+// Where a tile's trunk features come from.  RELU (ReLU | tanh) and TLN (layer_N) describe the trunk where the step runs it (Fused, Episode).
+//   XT:      feature-major xT in HBM, written by a features launch of its own.
+//   Fused:   every wave of the workgroup runs the (narrow-input) trunk of the tile itself with the weights in registers (mlp_trunk16r.h):
+//            its output in the accumulator layout IS the B operand of the W_ih products, and the features launch (~10 us per step) disappears.
+//   Lds:     xs[b][lane] = features 16 b + 4 q .. + 3 of row n, written behind a barrier by the wave that ran the trunk of a wide-input
+//            network in the same workgroup (mlp_wide16.h, wide_recurrent_step_dual_kernel).
+//   Episode: one step of a one-launch recurrent episode: the fused trunk with its weights in LDS, the tile named by `ep` (below).
+enum class Step3Src { XT, Fused, Lds, Episode };
 // this wave's operands of a step: loaded up front (all requests before the first wait), then any number of tiles
 template <int TLN>
 struct Step3W {
@@ -106,7 +108,7 @@ struct Step3W {
   Trunk16R<TLN> tw;
   g4_t bir, biz, bin, bhr, bhz, bhn, nw4, nb4, hw[2];
 };
-template <int TR, int TLN>
+template <Step3Src SRC, int TLN>
 __device__ __forceinline__ void gru_step3_load(Step3W<TLN> &W, const GruFwdArgs &p, const int w, const int n, const int q) {
   const int A = p.A;
   g4_t (&wi)[3][4] = W.wi, (&wh)[3][4] = W.wh;
@@ -118,7 +120,7 @@ __device__ __forceinline__ void gru_step3_load(Step3W<TLN> &W, const GruFwdArgs 
 #pragma unroll
       for (int b = 0; b < 4; ++b) { wi[g][b] = g4_load(ri + g * HID * HID + 16 * b); wh[g][b] = g4_load(rh + g * HID * HID + 16 * b); }
   }
-  if constexpr (TR == 1 || TR == 2) trunk16r_load<TLN>(W.tw, p.params, p.off, p.desc, n, q);
+  if constexpr (SRC == Step3Src::Fused) trunk16r_load<TLN>(W.tw, p.params, p.off, p.desc, n, q);
   const int u0 = 16 * w + 4 * q;                                // this lane's four hidden units
   W.bir = g4_load(p.params + p.off.gru_bih + u0); W.biz = g4_load(p.params + p.off.gru_bih + HID + u0); W.bin = g4_load(p.params + p.off.gru_bih + 2 * HID + u0);
   W.bhr = g4_load(p.params + p.off.gru_bhh + u0); W.bhz = g4_load(p.params + p.off.gru_bhh + HID + u0); W.bhn = g4_load(p.params + p.off.gru_bhh + 2 * HID + u0);
@@ -132,40 +134,40 @@ __device__ __forceinline__ void gru_step3_load(Step3W<TLN> &W, const GruFwdArgs 
   }
 }
 
-// TR 3: the tile's trunk features arrive through LDS, xs[b][lane] = features 16 b + 4 q .. + 3 of row n (written by the wave that
-// ran the trunk of a wide-input network in the same workgroup, behind a barrier: mlp_wide16.h, wide_recurrent_step_dual_kernel)
-// TR 4 | 5: one step of the one-launch recurrent episode (rollout_spread_rec.h; fused ReLU | tanh trunk with its weights in LDS).
-// TR 6 | 7: the same step for the SMAC-shaped episode (rollout_smac_rec.h): up to MAPPO_MAX_ACTIONS actions, and the sampling lanes
-// take the row's available_actions from ep->avail (the tile's [16][A] rows of the step, or NULL).
-// The workgroup holds TWO networks of four waves each, which come through here side by side (every barrier below is passed by
-// both; each has its own Step3Shared); `ep` (Step3Ep) names the tile: input rows, previous state and masks in LDS, buffer rows
-// ep->row0 .. + ep->R - 1 of slot offset ep->so, sampling counter ep->ctr.  The new state goes to the next step's LDS tile and
-// stays in *h_keep for the caller, which stores it once the env step has said whether the row's episode ended.
-struct Step3NoEp {};
-template <int HM, int TR, int TLN, class EP = Step3NoEp>
+// Episode: the workgroup holds TWO networks of four waves each, which come through here side by side (every barrier below is
+// passed by both; each has its own Step3Shared); `ep` names the tile: input rows, previous state and masks in LDS, buffer rows
+// ep->row0 .. + ep->R - 1 of slot offset ep->so, sampling counter ep->ctr, the tile's [16][A] available_actions rows of the step
+// (ep->avail, or NULL).  The new state goes to the next step's LDS tile and stays in *h_keep for the caller, which stores it once
+// the env step has said whether the row's episode ended.  What differs between episodes sits behind the EP type: EP::HEAD_BLOCKS
+// (the 16-action head blocks the entry point admits: 2, or 1 and the second block's products are compiled out) and two hooks
+// behind the trunk: ep->late() (a wave whose GRU slices W.wi / W.wh wait in LDS takes them) and ep->fill(...) (a wave whose biases,
+// rnn.norm vectors and head rows wait in LDS takes them into this function's locals; W is not written).
+struct Step3NoEp { static constexpr int HEAD_BLOCKS = 2; };
+template <int HM, Step3Src SRC, bool RELU, int TLN, class EP = Step3NoEp>
 __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruFwdArgs &p, Step3Shared &sh, const int bid, const int nb,
                                                 const float4 *xs = nullptr, const EP *ep = nullptr, g4_t *h_keep = nullptr) {
+  constexpr bool EPI = SRC == Step3Src::Episode;
   const int lane = threadIdx.x & (WAVE - 1), n = lane & 15, q = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)) & (TR >= 4 ? 3 : ~0);
-  const int n_tiles = TR >= 4 ? 1 : (p.Nc + 15) / 16;
-  int64_t so = 0;                                               // slot offset of the outputs (TR >= 4: step t of the episode)
-  if constexpr (TR >= 4) so = ep->so;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)) & (EPI ? 3 : ~0);
+  const int n_tiles = EPI ? 1 : (p.Nc + 15) / 16;
+  int64_t so = 0;                                               // slot offset of the outputs (Episode: step t of the episode)
+  if constexpr (EPI) so = ep->so;
   const int64_t B = p.Nc;                                       // L == 1: column = sequence
   const int A = p.A;
-  if constexpr (TR == 4 || TR == 5) __builtin_assume(A <= 16);  // (the spread episode's entry point takes 5 actions: no second head block)
+  if constexpr (EP::HEAD_BLOCKS < 2) __builtin_assume(A <= 16);
   const int u0 = 16 * w + 4 * q;
   const g4_t (&wi)[3][4] = W.wi, (&wh)[3][4] = W.wh;
   const Trunk16R<TLN> &tw = W.tw;
   g4_t bir = W.bir, biz = W.biz, bin = W.bin, bhr = W.bhr, bhz = W.bhz, bhn = W.bhn, nw4 = W.nw4, nb4 = W.nb4;
-  g4_t hw[2] = {W.hw[0], W.hw[1]};                              // (assigned again only by TR 6 | 7, behind the trunk)
+  g4_t hw[2] = {W.hw[0], W.hw[1]};                              // (assigned again only by ep->fill, behind the trunk)
   for (int tile = bid; tile < n_tiles; tile += nb) {
     int c = tile * 16 + n;
     bool ok = c < p.Nc;
-    if constexpr (TR >= 4) { c = ep->row0 + n; ok = n < ep->R; }
+    if constexpr (EPI) { c = ep->row0 + n; ok = n < ep->R; }
     const int cc = ok ? c : 0;
-    const int64_t hrow = (TR < 4 && p.h0_rows) ? (int64_t)p.h0_rows[cc] : (int64_t)cc;
+    const int64_t hrow = (!EPI && p.h0_rows) ? (int64_t)p.h0_rows[cc] : (int64_t)cc;
     float mk;
-    if constexpr (TR >= 4) {
+    if constexpr (EPI) {
       mk = ok ? ep->mk[n] : 0.f;
     } else if (p.dones) {
       const int env = cc / p.done_M;
@@ -176,33 +178,32 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
       mk = ok ? p.masks[p.rows ? (int64_t)p.rows[cc] : (int64_t)cc] : 0.f;
     }
     uint32_t dead = 0u;
-    if constexpr (TR >= 6) {
+    if constexpr (EPI) {
       if (HM == 2 && ep->avail && w == 0 && q == 0) dead = avail_dead_mask(ep->avail + (ok ? n : 0) * A, A);
     } else {
       if (HM == 2 && p.avail && w == 0 && q == 0) dead = avail_dead_mask(p.avail + (int64_t)cc * A, A);    // the sampling lanes
     }
     g4_t x[4], hm[4];
-    if constexpr (TR == 3) {
+    if constexpr (SRC == Step3Src::Lds) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         const float4 t = xs[b * 64 + lane];
         x[b][0] = t.x; x[b][1] = t.y; x[b][2] = t.z; x[b][3] = t.w;
         hm[b] = g4_load(p.h0 + hrow * HID + 16 * b + 4 * q);
       }
-    } else if constexpr (TR >= 4) {
+    } else if constexpr (EPI) {
       const int D = p.desc.in_dim;
       f32x4 xin[4];
 #pragma unroll
       for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int i = 0; i < 4; ++i) xin[b][i] = ep->xrow[min(16 * b + 4 * q + i, D - 1)];
-      trunk16r_apply<TR == 4 || TR == 6, TLN>(ep->tw, xin, x, D, ok, p.desc.use_feature_norm != 0, q);
+      trunk16r_apply<RELU, TLN>(ep->tw, xin, x, D, ok, p.desc.use_feature_norm != 0, q);
       ep->late();                                               // a wave whose GRU slices (W.wi / W.wh) wait in LDS takes them now
-      // the SMAC episode's waves take their biases, rnn.norm vectors and head rows from LDS here, behind the trunk (W is not written)
-      if constexpr (TR >= 6) ep->fill(bir, biz, bin, bhr, bhz, bhn, nw4, nb4, hw);
+      ep->fill(bir, biz, bin, bhr, bhz, bhn, nw4, nb4, hw);
 #pragma unroll
       for (int b = 0; b < 4; ++b) hm[b] = *reinterpret_cast<const g4_t *>(ep->hs + n * ep->hs_stride + 16 * b + 4 * q);
-    } else if constexpr (TR != 0) {
+    } else if constexpr (SRC == Step3Src::Fused) {
       const int D = p.desc.in_dim;
       const float *xr = p.x_rows + (int64_t)cc * D;
       f32x4 xin[4];
@@ -212,7 +213,7 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
         for (int i = 0; i < 4; ++i) xin[b][i] = xr[min(16 * b + 4 * q + i, D - 1)];
 #pragma unroll
       for (int b = 0; b < 4; ++b) hm[b] = g4_load(p.h0 + hrow * HID + 16 * b + 4 * q);
-      trunk16r_apply<TR == 1, TLN>(tw, xin, x, D, ok, p.desc.use_feature_norm != 0, q);
+      trunk16r_apply<RELU, TLN>(tw, xin, x, D, ok, p.desc.use_feature_norm != 0, q);
     } else {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
@@ -247,7 +248,7 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
       const float gn = tanhf_(ain[i] + gr * ahn[i]);
       h[i] = (1.f - gz) * gn + gz * hprev[i];
     }
-    if constexpr (TR >= 4) {
+    if constexpr (EPI) {
       *reinterpret_cast<g4_t *>(ep->hs_next + n * ep->hs_stride + u0) = h;
       *h_keep = h;
     } else if (p.h_last && ok) {
@@ -300,12 +301,12 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
         wave_lds_sync();
         if (q == 0 && ok) {
           uint64_t ctr;
-          if constexpr (TR >= 4) ctr = ep->ctr; else ctr = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);
+          if constexpr (EPI) ctr = ep->ctr; else ctr = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);
           float action, logp;
           categorical_act_mask(&sh.tZ[n][0], A, dead, p.deterministic != 0, p.seed, ctr, (uint64_t)c, action, logp);
           p.actions[so + c] = action;
           p.logp[so + c] = logp;
-          if constexpr (TR >= 4) ep->act[n] = action;
+          if constexpr (EPI) ep->act[n] = action;
         }
       }
     }
@@ -313,12 +314,12 @@ __device__ __forceinline__ void gru_step3_tiles(const Step3W<TLN> &W, const GruF
   }
 }
 
-template <int HM, int TR = 0, int TLN = 0>
+template <int HM, Step3Src SRC = Step3Src::XT, bool RELU = false, int TLN = 0>
 __device__ __forceinline__ void gru_step3_body(const GruFwdArgs &p, Step3Shared &sh, const int bid, const int nb) {
   const int lane = threadIdx.x & (WAVE - 1), w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE)), n = lane & 15, q = lane >> 4;
   if (bid >= (p.Nc + 15) / 16) return;
   Step3W<TLN> W;
-  gru_step3_load<TR, TLN>(W, p, w, n, q);
-  gru_step3_tiles<HM, TR, TLN>(W, p, sh, bid, nb);
+  gru_step3_load<SRC, TLN>(W, p, w, n, q);
+  gru_step3_tiles<HM, SRC, RELU, TLN>(W, p, sh, bid, nb);
 }
 

@@ -32,12 +32,12 @@ __global__ __launch_bounds__(256, 1) void wide_recurrent_step_dual_kernel(WideRe
   // trunk's first MFMA waited for)
   if (actor) {
     wide_forward16_sk_body<RELU, LN, 4>(r.d.wa, r.d.a, lds, sh, bid, nb, reinterpret_cast<float *>(sX),
-                                        [&]() __attribute__((always_inline)) { gru_step3_load<3, 0>(W, r.ga, wv, n, q); });
-    gru_step3_tiles<2, 3, 0>(W, r.ga, s3, bid, nb, sX);
+                                        [&]() __attribute__((always_inline)) { gru_step3_load<Step3Src::Lds, 0>(W, r.ga, wv, n, q); });
+    gru_step3_tiles<2, Step3Src::Lds, false, 0>(W, r.ga, s3, bid, nb, sX);
   } else {
     wide_forward16_sk_body<RELU, LN, 4>(r.d.wc, r.d.c, lds, sh, bid, nb, reinterpret_cast<float *>(sX),
-                                        [&]() __attribute__((always_inline)) { gru_step3_load<3, 0>(W, r.gc, wv, n, q); });
-    gru_step3_tiles<1, 3, 0>(W, r.gc, s3, bid, nb, sX);
+                                        [&]() __attribute__((always_inline)) { gru_step3_load<Step3Src::Lds, 0>(W, r.gc, wv, n, q); });
+    gru_step3_tiles<1, Step3Src::Lds, false, 0>(W, r.gc, s3, bid, nb, sX);
   }
 }
 #undef GS

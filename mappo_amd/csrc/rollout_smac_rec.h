@@ -8,7 +8,7 @@
 //
 // Ownership: a workgroup owns G = floor(16 / M) whole environments = G M consecutive buffer rows of one 16-row tile — whole
 // environments, so that dones_env = all_m dones[n][m] is local to the tile — and walks all T steps alone.  Its eight waves are the
-// two 4-wave groups of gru_step3_tiles (waves 0..3 the actor, 4..7 the critic; source TR 6 | 7), so each value is the one the
+// two 4-wave groups of gru_step3_tiles (waves 0..3 the actor, 4..7 the critic; source Step3Src::Episode), so each value is the one the
 // stepwise launches compute for the row: same MFMA sequence, same LayerNorm exchange, same order of the partial logits, same
 // categorical_act_mask call keyed by (seed, counter + k, buffer row).
 //   * Registers: the GRU slices of a wave (96 VGPRs) for the episode; both trunks once into LDS (the EplMap image of mlp_ep16l.h
@@ -28,16 +28,14 @@
 //     tile k and of mask k is done) — and B_k (input tile k + 1 and mask k + 1 are in LDS).  No wave returns early; the idle lanes
 //     of a partial tile pass every barrier.
 #pragma once
-#include "gru_step3.h"
-#include "mlp_ep16l.h"
+#include "rollout_rec_frame.h"
 
-#define SMREC_HS 68                                                 // row stride of the LDS state tiles (rows 4 banks apart)
-#define SMREC_XS 68                                                 // ... of the LDS input tiles
-#define SMREC_WAVES 8
+#define SMREC_XS 68                                                 // row stride of the LDS input tiles (rows 4 banks apart)
 #define SMREC_MAX_M 16
 
 template <int LN>
-struct Step3EpSmac {
+struct Step3EpSmac : Step3EpFrame<LN> {
+  static constexpr int HEAD_BLOCKS = 2;                             // up to MAPPO_MAX_ACTIONS actions
   // The biases, rnn.norm vectors and head rows of a wave (40 VGPRs) are not needed while the trunk runs, where the register
   // pressure peaks (the tanh trunk by itself takes what rollout_spread_rec.h has left): they wait in LDS and come back behind the
   // trunk, every step.  The vectors depend on (wave, q) only, the head rows on the lane.
@@ -49,16 +47,7 @@ struct Step3EpSmac {
     bir = vs[0]; biz = vs[1]; bin = vs[2]; bhr = vs[3]; bhz = vs[4]; bhn = vs[5]; nw4 = vs[6]; nb4 = vs[7];
     hw[0] = hws[0]; hw[1] = hws[WAVE];
   }
-  Trunk16L<LN> tw;                 // this lane's view of its network's trunk image
-  const float *xrow;               // this lane's input row (LDS)
-  const float *hs;                 // [16][hs_stride] previous states of the tile
-  float *hs_next;                  // ... of the next step
-  const float *mk;                 // [16] masks of the step
-  float *act;                      // [16] sampled actions of the tile rows
   const float *avail;              // [16][A] available_actions of the tile rows for this step (LDS), or NULL
-  int hs_stride, row0, R;          // first buffer row of the tile, rows that exist
-  int64_t so;                      // k * B
-  uint64_t ctr;                    // sampling counter of the step
 };
 
 struct SmacRecArgs {
@@ -76,32 +65,25 @@ struct SmacRecArgs {
 template <int LN>
 struct SmrecLds {
   static constexpr int IMG = EplMap<LN>::wh;                        // the trunk's part of the image
-  static constexpr int imgA = 0, imgC = IMG, XA = 2 * IMG, XC = XA + 16 * SMREC_XS, hsA = XC + 16 * SMREC_XS, hsC = hsA + 2 * 16 * SMREC_HS,
-                       mk = hsC + 2 * 16 * SMREC_HS, act = mk + 16, dn = act + 16, av = dn + 16, vst = av + 16 * MAPPO_MAX_ACTIONS, hst = vst + SMREC_WAVES * 4 * 8 * 4,
-                       total = hst + SMREC_WAVES * 2 * WAVE * 4;
+  static constexpr int imgA = 0, imgC = IMG, XA = 2 * IMG, XC = XA + 16 * SMREC_XS, hsA = XC + 16 * SMREC_XS, hsC = hsA + 2 * 16 * REC_HS,
+                       mk = hsC + 2 * 16 * REC_HS, act = mk + 16, dn = act + 16, av = dn + 16, vst = av + 16 * MAPPO_MAX_ACTIONS, hst = vst + REC_WAVES * 4 * 8 * 4,
+                       total = hst + REC_WAVES * 2 * WAVE * 4;
 };
 
 // one network's four waves over the whole episode
-template <int HM, int TR, int LN>
+template <int HM, bool RELU, int LN>
 __device__ __forceinline__ void smac_rec_role(const SmacRecArgs &e, const GruFwdArgs &p, Step3Shared &sh, float *lds, float *rnn, const int w) {
   typedef SmrecLds<LN> Ld;
-  const int lane = threadIdx.x & (WAVE - 1), n = lane & 15, q = lane >> 4;
   const int M = e.M, G = e.G, T = e.T;
   const int Dn = p.desc.in_dim;                                     // the input width of THIS network (actor: D, critic: S)
   const int A = e.a.A;
   const int64_t B = (int64_t)e.N * M;
-  const int i0 = (int)blockIdx.x * G * M;
-  const int Rv = (int)(B - i0 < G * M ? B - i0 : G * M);            // rows of the tile that exist (whole environments)
-  const bool ok = n < Rv;
-  const int jr = ok ? n : 0;
-  float *X = lds + (HM == 2 ? Ld::XA : Ld::XC), *mk = lds + Ld::mk, *act = lds + Ld::act, *dn = lds + Ld::dn, *AV = lds + Ld::av;
-  float *hs = lds + (HM == 2 ? Ld::hsA : Ld::hsC);
-  const float *img = lds + (HM == 2 ? Ld::imgA : Ld::imgC);
   Step3W<LN> W;
-  gru_step3_load<0, LN>(W, p, w, n, q);                             // GRU slices, biases, head rows: registers (the trunk: LDS)
-  const uint64_t ctr0 = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);      // read once: the word is fixed for the launch
   Step3EpSmac<LN> ep;
-  ep.tw.m = img + n * EPL_WS + 4 * q; ep.tw.v = img + 4 * q;
+  const RecRole r = rec_role_begin<HM, Ld>(p, lds, B, G, M, w, W, ep);
+  const int lane = r.lane, n = r.n, q = r.q, i0 = r.i0, Rv = r.Rv;
+  const bool ok = r.ok;
+  float *X = lds + (HM == 2 ? Ld::XA : Ld::XC), *mk = r.mk, *dn = lds + Ld::dn, *AV = lds + Ld::av;
   {
     const int gw = HM == 2 ? w : w + 4;                             // this wave among the workgroup's eight
     g4_t *vs = reinterpret_cast<g4_t *>(lds + Ld::vst) + (gw * 4 + q) * 8, *hws = reinterpret_cast<g4_t *>(lds + Ld::hst) + gw * 2 * WAVE + lane;
@@ -109,8 +91,7 @@ __device__ __forceinline__ void smac_rec_role(const SmacRecArgs &e, const GruFwd
     hws[0] = W.hw[0]; hws[WAVE] = W.hw[1];
     ep.vs = vs; ep.hws = hws;
   }
-  ep.mk = mk; ep.act = act; ep.hs_stride = SMREC_HS; ep.row0 = i0; ep.R = Rv;
-  ep.xrow = X + jr * SMREC_XS;
+  ep.xrow = X + r.jr * SMREC_XS;
   ep.avail = (HM == 2 && e.e_avail) ? AV : nullptr;                 // the rows' available_actions of the step: slot 0, then what the insert put there
   const int gt = w * WAVE + lane;                                   // this lane among the 256 of its network
   const bool flag_lane = HM == 1 && w == 0 && lane < 16 && ok;      // the lanes that derive the masks of row i0 + n
@@ -135,11 +116,9 @@ __device__ __forceinline__ void smac_rec_role(const SmacRecArgs &e, const GruFwd
       }
       if (flag_lane) { dbyte = e.e_done[so + i0 + n]; rw = e.e_rew[(int64_t)k * e.N + (i0 + n) / M]; }
     }
-    ep.hs = hs + (k & 1) * 16 * SMREC_HS;
-    ep.hs_next = hs + ((k + 1) & 1) * 16 * SMREC_HS;
-    ep.so = so; ep.ctr = ctr0 + (uint64_t)k;
+    rec_step_begin(ep, r, k, so);
     g4_t h;
-    gru_step3_tiles<HM, TR, LN>(W, p, sh, 0, 1, nullptr, &ep, &h);  // its last barrier is A_k
+    gru_step3_tiles<HM, Step3Src::Episode, RELU, LN>(W, p, sh, 0, 1, nullptr, &ep, &h);      // its last barrier is A_k
     // ---- what insert_smac_body writes into slot k + 1 (rewards: slot k); the input tiles and the mask of step k + 1 -> LDS ----
     {
       float *xd = dst + (so + B + i0) * Dn;
@@ -170,31 +149,24 @@ __device__ __forceinline__ void smac_rec_role(const SmacRecArgs &e, const GruFwd
       }
     }
     __syncthreads();                                                // B_k
-    // ---- the new state x (1 - dones_env) -> slot k + 1 ----
-    if (ok) {
-      const float keep = mk[n];
-      g4u_t o; o[0] = h[0] * keep; o[1] = h[1] * keep; o[2] = h[2] * keep; o[3] = h[3] * keep;
-      *reinterpret_cast<g4u_t *>(rnn + (so + B + i0 + n) * HID + 16 * w + 4 * q) = o;
-    }
+    rec_store_state(rnn, h, r, lane, so + B + i0, w);
   }
 }
 
-template <int TR, int LN>
-__global__ __launch_bounds__(SMREC_WAVES * WAVE, 1) void rollout_episode_smac_rec_kernel(SmacRecArgs e) {
+template <bool RELU, int LN>
+__global__ __launch_bounds__(REC_WAVES * WAVE, 1) void rollout_episode_smac_rec_kernel(SmacRecArgs e) {
   typedef SmrecLds<LN> Ld;
   extern __shared__ __align__(16) float lds[];
   __shared__ Step3Shared sh[2];
-  const int tid = threadIdx.x, nt = SMREC_WAVES * WAVE;
+  const int tid = threadIdx.x, nt = REC_WAVES * WAVE;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
   {
-    // ---- prologue, every thread: both trunks, the tile's rows of slot 0 (observations, share rows, states, masks) -> LDS ----
     const int M = e.M, D = e.a.desc.in_dim, S = e.c.desc.in_dim;
     const int64_t B = (int64_t)e.N * M;
     const int i0 = (int)blockIdx.x * e.G * M;
     const int Rv = (int)(B - i0 < e.G * M ? B - i0 : e.G * M);
-    epl_stage<LN, 0>(lds + Ld::imgA, e.a.params, e.a.off, e.a.desc);
-    epl_stage<LN, 0>(lds + Ld::imgC, e.c.params, e.c.off, e.c.desc);
-    for (int k = tid; k < 16 * SMREC_XS; k += nt) {
+    rec_stage<LN, Ld>(lds, e.a, e.c, e.rnn_a, e.rnn_c, e.mask_buf, i0, Rv);
+    for (int k = tid; k < 16 * SMREC_XS; k += nt) {                 // the input tiles: rows SMREC_XS apart
       const int row = k / SMREC_XS, col = k - row * SMREC_XS;
       lds[Ld::XA + k] = (row < Rv && col < D) ? e.obs_buf[(int64_t)(i0 + row) * D + col] : 0.f;
       lds[Ld::XC + k] = (row < Rv && col < S) ? e.share_buf[(int64_t)(i0 + row) * S + col] : 0.f;
@@ -203,15 +175,10 @@ __global__ __launch_bounds__(SMREC_WAVES * WAVE, 1) void rollout_episode_smac_re
       const int A = e.a.A;
       for (int k = tid; k < 16 * MAPPO_MAX_ACTIONS; k += nt) lds[Ld::av + k] = k < Rv * A ? e.avail_buf[(int64_t)i0 * A + k] : 1.f;
     }
-    for (int k = tid; k < 16 * HID; k += nt) {
-      const int row = k >> 6, u = k & 63;
-      lds[Ld::hsA + row * SMREC_HS + u] = row < Rv ? e.rnn_a[(int64_t)(i0 + row) * HID + u] : 0.f;
-      lds[Ld::hsC + row * SMREC_HS + u] = row < Rv ? e.rnn_c[(int64_t)(i0 + row) * HID + u] : 0.f;
-    }
-    if (tid < 16) { lds[Ld::mk + tid] = tid < Rv ? e.mask_buf[i0 + tid] : 0.f; lds[Ld::act + tid] = 0.f; lds[Ld::dn + tid] = 0.f; }
+    if (tid < 16) lds[Ld::dn + tid] = 0.f;
   }
-  if (wave < 4) smac_rec_role<2, TR, LN>(e, e.a, sh[0], lds, e.rnn_a, wave);
-  else smac_rec_role<1, TR, LN>(e, e.c, sh[1], lds, e.rnn_c, wave - 4);
+  if (wave < 4) smac_rec_role<2, RELU, LN>(e, e.a, sh[0], lds, e.rnn_a, wave);
+  else smac_rec_role<1, RELU, LN>(e, e.c, sh[1], lds, e.rnn_c, wave - 4);
 }
 
 extern "C" int mappo_rollout_episode_smac_recurrent(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
@@ -223,21 +190,10 @@ extern "C" int mappo_rollout_episode_smac_recurrent(const float *actor_params, c
                                                     float *active_mask_buf, float *rnn_states, float *rnn_states_critic, float *actions,
                                                     float *logp, float *values, int32_t centralized, mappo_stream_t stream) {
   const char *who = "rollout_episode_smac_recurrent";
-  MAPPO_REQUIRE(actor_desc && critic_desc, "%s: bad arguments (null pointer)", who);
-  MAPPO_REQUIRE(actor_desc->recurrent && critic_desc->recurrent, "%s: needs recurrent network descriptors (actor and critic)", who);
-  if (int rc = check_desc_common(actor_desc, who)) return rc;      // (actor out_dim <= MAPPO_MAX_ACTIONS among them)
-  if (int rc = check_desc_common(critic_desc, who)) return rc;
-  MAPPO_REQUIRE(actor_desc->in_dim <= MAXD && critic_desc->in_dim <= MAXD, "%s: in_dim %d / %d: both networks must be narrow (<= %d); wider "
-                "inputs step one launch at a time", who, actor_desc->in_dim, critic_desc->in_dim, MAXD);
-  MAPPO_REQUIRE(actor_desc->layer_N <= 1 && critic_desc->layer_N <= 1, "%s: layer_N %d / %d: at most one hidden layer (layer_N <= 1)", who,
-                actor_desc->layer_N, critic_desc->layer_N);
-  MAPPO_REQUIRE(actor_desc->layer_N == critic_desc->layer_N && actor_desc->use_relu == critic_desc->use_relu,
-                "%s: actor and critic must share layer_N and the activation", who);
-  MAPPO_REQUIRE(critic_desc->out_dim == 1, "%s: critic out_dim must be 1", who);
+  if (int rc = rec_episode_check(actor_desc, critic_desc, N, M, who)) return rc;
   MAPPO_REQUIRE(M >= 1 && M <= SMREC_MAX_M, "%s: M=%d out of range (1 .. %d agents: a 16-row tile holds whole environments)", who, M,
                 SMREC_MAX_M);
   MAPPO_REQUIRE(T >= 1 && N >= 1, "%s: bad shape T=%d N=%d", who, T, N);
-  MAPPO_REQUIRE((int64_t)N * M <= INT32_MAX / MAXD, "%s: N*M = %lld rows exceed the int32 row indices", who, (long long)N * M);
   if (!centralized)
     MAPPO_REQUIRE(critic_desc->in_dim == actor_desc->in_dim, "%s: critic in_dim %d != actor in_dim %d (not centralized: the critic reads obs)",
                   who, critic_desc->in_dim, actor_desc->in_dim);
@@ -248,30 +204,18 @@ extern "C" int mappo_rollout_episode_smac_recurrent(const float *actor_params, c
                 "neither NULL)", who);
   MAPPO_CLEAR_STICKY();
   SmacRecArgs e = {};
-  GruFwdArgs &a = e.a, &c = e.c;
-  a.params = actor_params; a.off = net_offsets(*actor_desc); a.desc = *actor_desc; a.L = 1; a.Nc = N * M; a.A = actor_desc->out_dim; a.head_mode = 2;
-  a.actions = actions; a.logp = logp; a.deterministic = deterministic; a.seed = seed; a.counter = counter; a.counter_dev = counter_dev;
-  c.params = critic_params; c.off = net_offsets(*critic_desc); c.desc = *critic_desc; c.L = 1; c.Nc = N * M; c.A = 1; c.head_mode = 1; c.out = values;
+  rec_episode_args(e.a, e.c, actor_params, actor_desc, critic_params, critic_desc, N * M, deterministic, seed, counter, counter_dev, actions, logp,
+                   values);
   e.e_obs = env_obs; e.e_share = centralized ? env_share_obs : env_obs; e.e_avail = env_avail; e.e_rew = env_rewards; e.e_done = env_dones;
   e.e_bad = env_bad_transition;
   e.obs_buf = obs_buf; e.share_buf = share_buf; e.avail_buf = avail_buf; e.rew_buf = rew_buf; e.mask_buf = mask_buf; e.bad_buf = bad_mask_buf;
   e.active_buf = active_mask_buf; e.rnn_a = rnn_states; e.rnn_c = rnn_states_critic;
   e.T = T; e.N = N; e.M = M; e.G = 16 / M;
-  const dim3 grid((unsigned)((N + e.G - 1) / e.G)), block(SMREC_WAVES * WAVE);
-  hipStream_t st = as_stream(stream);
-  const bool relu = actor_desc->use_relu != 0;
-  constexpr int LDS_MAX = LDS_DYN_MAX - (int)(2 * sizeof(Step3Shared));
-  int rc;
-  if (actor_desc->layer_N == 0) {
-    const size_t lb = sizeof(float) * SmrecLds<0>::total;
-    rc = relu ? launch_kernel<rollout_episode_smac_rec_kernel<6, 0>, LDS_MAX>(who, grid, block, lb, st, e)
-              : launch_kernel<rollout_episode_smac_rec_kernel<7, 0>, LDS_MAX>(who, grid, block, lb, st, e);
-  } else {
-    const size_t lb = sizeof(float) * SmrecLds<1>::total;
-    rc = relu ? launch_kernel<rollout_episode_smac_rec_kernel<6, 1>, LDS_MAX>(who, grid, block, lb, st, e)
-              : launch_kernel<rollout_episode_smac_rec_kernel<7, 1>, LDS_MAX>(who, grid, block, lb, st, e);
-  }
-  if (rc) return rc;
-  MAPPO_CHECK_LAUNCH("rollout_episode_smac_recurrent");
+  const dim3 grid((unsigned)((N + e.G - 1) / e.G)), block(REC_WAVES * WAVE);
+  if (int rc = dispatch_relu_ln<1>(actor_desc->use_relu != 0, actor_desc->layer_N, [&](auto R, auto L) {
+        return launch_kernel<rollout_episode_smac_rec_kernel<R.value, L.value>, REC_LDS_MAX>(who, grid, block, sizeof(float) * SmrecLds<L.value>::total, as_stream(stream), e);
+      }))
+    return rc;
+  MAPPO_CHECK_LAUNCH(who);
   return MAPPO_OK;
 }

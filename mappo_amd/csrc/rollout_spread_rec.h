@@ -7,7 +7,7 @@
 // Ownership is rollout_spread.h's: a workgroup owns G = floor(16 / M) whole environments = G M consecutive buffer rows of one
 // 16-row tile and walks all T steps alone.  Its eight waves are the two 4-wave groups of gru_step3_tiles — waves 0..3 the actor,
 // 4..7 the critic, wave w of a group owning hidden units [16 w, 16 w + 16) — and every row goes through that function (source
-// TR 4 | 5), so each value is the one mappo_recurrent_step_dual computes for the row: same MFMA sequence, same LayerNorm exchange,
+// Step3Src::Episode), so each value is the one mappo_recurrent_step_dual computes for the row: same MFMA sequence, same LayerNorm exchange,
 // same order of the partial logits, same categorical_act_mask call keyed by the buffer row.
 //   * Registers: the GRU slices, biases and head rows of a wave (Step3W, ~136 VGPRs) stay in registers for the episode; the trunk
 //     (another ~180 at layer_N 1) does not fit beside them, so both trunks are staged once into LDS (the EplMap image of
@@ -26,14 +26,14 @@
 //     are in LDS, every read of observation tile t is done) — and B_t (observation tile t + 1 and masks[t + 1] are in LDS).
 #pragma once
 #include "mpe_core.h"
-#include "gru_step3.h"
+#include "rollout_rec_frame.h"
 
-#define SREC_HS 68                                                  // row stride of the LDS state tiles (rows 4 banks apart)
-#define SREC_WAVES 8
 #define SREC_ES (4 * MPE_MAX_M + 2 * MPE_MAX_L + 1)                 // doubles of one env lane's state row (agent_pos | agent_vel | landmark_pos, odd stride)
 
 template <int LN, bool LATE>
-struct Step3Ep {
+struct Step3Ep : Step3EpFrame<LN> {
+  static constexpr int HEAD_BLOCKS = 1;                             // the entry point takes 5 actions: no second head block
+  static constexpr const float *avail = nullptr;                    // simple_spread has no available_actions
   // LATE (the env wave): the GRU slices are fetched from their LDS copy behind the trunk, so that they are live only from the
   // GRU products to the end of the tile function — not beside the trunk's temporaries, and not while the environments step
   Step3W<LN> *Wl;
@@ -46,15 +46,7 @@ struct Step3Ep {
         for (int b = 0; b < 4; ++b) { Wl->wi[g][b] = stash[(8 * g + 2 * b) * WAVE]; Wl->wh[g][b] = stash[(8 * g + 2 * b + 1) * WAVE]; }
     }
   }
-  Trunk16L<LN> tw;                 // this lane's view of its network's trunk image
-  const float *xrow;               // this lane's input row (LDS)
-  const float *hs;                 // [16][hs_stride] previous states of the tile
-  float *hs_next;                  // ... of the next step
-  const float *mk;                 // [16] masks of the step
-  float *act;                      // [16] sampled actions of the tile rows
-  int hs_stride, row0, R;          // first buffer row of the tile, rows that exist
-  int64_t so;                      // t * B
-  uint64_t ctr;                    // sampling counter of the step
+  __device__ __forceinline__ void fill(g4_t &, g4_t &, g4_t &, g4_t &, g4_t &, g4_t &, g4_t &, g4_t &, g4_t (&)[2]) const {}    // biases, head rows: the Step3W given
 };
 
 struct SpreadRecArgs {
@@ -69,34 +61,25 @@ struct SpreadRecArgs {
 template <int LN>
 struct SrecLds {
   static constexpr int IMG = EplMap<LN>::wh;                        // the trunk's part of the image
-  static constexpr int imgA = 0, imgC = IMG, X = 2 * IMG, X0 = X + 16 * MAXD, hsA = X0 + 16 * MAXD, hsC = hsA + 2 * 16 * SREC_HS,
-                       mk = hsC + 2 * 16 * SREC_HS, act = mk + 16, stash = act + 16, envs = stash + 34 * 4 * WAVE,
+  static constexpr int imgA = 0, imgC = IMG, X = 2 * IMG, X0 = X + 16 * MAXD, hsA = X0 + 16 * MAXD, hsC = hsA + 2 * 16 * REC_HS,
+                       mk = hsC + 2 * 16 * REC_HS, act = mk + 16, stash = act + 16, envs = stash + 34 * 4 * WAVE,
                        total = envs + 16 * 2 * SREC_ES;
 };
 
 // one network's four waves over the whole episode; ENV: this group's last wave also steps the environments
-template <int HM, int TR, int LN, bool ENV>
+template <int HM, bool RELU, int LN, bool ENV>
 __device__ __forceinline__ void spread_rec_role(const SpreadRecArgs &e, const GruFwdArgs &p, Step3Shared &sh, float *lds, float *rnn,
                                                 const int w) {
   typedef SrecLds<LN> Ld;
-  const int lane = threadIdx.x & (WAVE - 1), n = lane & 15, q = lane >> 4;
   const int M = e.env.M, G = e.G, T = e.T;
   const int D = e.a.desc.in_dim, S = e.c.desc.in_dim;
   const int64_t B = (int64_t)e.env.N * M;
-  const int n0 = (int)blockIdx.x * G, i0 = n0 * M;
-  const int Rv = (int)(B - i0 < G * M ? B - i0 : G * M);            // rows of the tile that exist (the last tile may be partial)
-  const bool ok = n < Rv;
-  const int jr = ok ? n : 0;
-  float *X = lds + Ld::X, *mk = lds + Ld::mk, *act = lds + Ld::act;
-  float *hs = lds + (HM == 2 ? Ld::hsA : Ld::hsC);
-  const float *img = lds + (HM == 2 ? Ld::imgA : Ld::imgC);
   Step3W<LN> W;
-  gru_step3_load<0, LN>(W, p, w, n, q);                             // GRU slices, biases, head rows: registers (the trunk: LDS)
-  const uint64_t ctr0 = p.counter + (p.counter_dev ? *p.counter_dev : 0ull);      // read once: the word is fixed for the launch
   Step3Ep<LN, ENV> ep;
+  const RecRole r = rec_role_begin<HM, Ld>(p, lds, B, G, M, w, W, ep);
+  const int lane = r.lane, n0 = (int)blockIdx.x * G, i0 = r.i0, Rv = r.Rv, jr = r.jr;
+  float *X = lds + Ld::X, *mk = r.mk, *act = r.act;
   ep.Wl = &W; ep.stash = reinterpret_cast<const g4_t *>(lds + Ld::stash) + lane;
-  ep.tw.m = img + n * EPL_WS + 4 * q; ep.tw.v = img + 4 * q;
-  ep.mk = mk; ep.act = act; ep.hs_stride = SREC_HS; ep.row0 = i0; ep.R = Rv;
   // The env wave (ENV: a role of its own, the critic's wave 3) keeps its operands in LDS as well: biases and head rows come back
   // at the top of every step, the GRU slices behind the trunk (Step3Ep::late) — all dead while the environments step.
   g4_t *stash = reinterpret_cast<g4_t *>(lds + Ld::stash) + lane;
@@ -131,11 +114,9 @@ __device__ __forceinline__ void spread_rec_role(const SpreadRecArgs &e, const Gr
     const int64_t so = (int64_t)t * B;
     if (HM == 2) ep.xrow = X + jr * D;
     else ep.xrow = t == 0 ? lds + Ld::X0 + jr * S : X + (e.centralized ? (jr / M) * S : jr * D);
-    ep.hs = hs + (t & 1) * 16 * SREC_HS;
-    ep.hs_next = hs + ((t + 1) & 1) * 16 * SREC_HS;
-    ep.so = so; ep.ctr = ctr0 + (uint64_t)t;
+    rec_step_begin(ep, r, t, so);
     g4_t h;
-    gru_step3_tiles<HM, TR, LN>(W, p, sh, 0, 1, nullptr, &ep, &h);  // its last barrier is A_t
+    gru_step3_tiles<HM, Step3Src::Episode, RELU, LN>(W, p, sh, 0, 1, nullptr, &ep, &h);      // its last barrier is A_t
     if (ENV) {
       // ---- environments: one lane each; obs -> the tile (rows lane M ..), rewards -> slot t, masks -> slot t + 1 and LDS ----
       int el = lane;
@@ -154,12 +135,7 @@ __device__ __forceinline__ void spread_rec_role(const SpreadRecArgs &e, const Gr
     // ---- what insert_mpe_rnn writes into slot t + 1: states * (1 - done), the observation tile, the share rows ----
     int sl = lane;
     asm volatile("" : "+v"(sl));            // the store addresses are made here, every step: hoisted, they sit in registers through the tile function
-    const int sn = sl & 15, sq = sl >> 4;
-    if (sn < Rv) {
-      const float keep = mk[sn];
-      g4u_t o; o[0] = h[0] * keep; o[1] = h[1] * keep; o[2] = h[2] * keep; o[3] = h[3] * keep;
-      *reinterpret_cast<g4u_t *>(rnn + (so + B + i0 + sn) * HID + 16 * w + 4 * sq) = o;
-    }
+    rec_store_state(rnn, h, r, sl, so + B + i0, w);
     const int k0 = w * WAVE + sl;
     if (HM == 2) {
       float *od = e.obs_buf + (so + B + i0) * D;
@@ -182,35 +158,27 @@ __device__ __forceinline__ void spread_rec_role(const SpreadRecArgs &e, const Gr
   }
 }
 
-template <int TR, int LN>
-__global__ __launch_bounds__(SREC_WAVES * WAVE, 1) void rollout_episode_spread_rec_kernel(SpreadRecArgs e) {
+template <bool RELU, int LN>
+__global__ __launch_bounds__(REC_WAVES * WAVE, 1) void rollout_episode_spread_rec_kernel(SpreadRecArgs e) {
   typedef SrecLds<LN> Ld;
   extern __shared__ __align__(16) float lds[];
   __shared__ Step3Shared sh[2];
-  const int tid = threadIdx.x, nt = SREC_WAVES * WAVE;
+  const int tid = threadIdx.x, nt = REC_WAVES * WAVE;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
   {
-    // ---- prologue, every thread: both trunks, the tile's rows of slot 0 (observations, share rows, states, masks) -> LDS ----
     const int M = e.env.M, D = e.a.desc.in_dim, S = e.c.desc.in_dim;
     const int64_t B = (int64_t)e.env.N * M;
     const int i0 = (int)blockIdx.x * e.G * M;
     const int Rv = (int)(B - i0 < e.G * M ? B - i0 : e.G * M);
-    epl_stage<LN, 0>(lds + Ld::imgA, e.a.params, e.a.off, e.a.desc);
-    epl_stage<LN, 0>(lds + Ld::imgC, e.c.params, e.c.off, e.c.desc);
-    for (int k = tid; k < 16 * MAXD; k += nt) {
+    rec_stage<LN, Ld>(lds, e.a, e.c, e.rnn_a, e.rnn_c, e.mask_buf, i0, Rv);
+    for (int k = tid; k < 16 * MAXD; k += nt) {                     // the input tiles: rows packed D | S apart
       lds[Ld::X + k] = k < Rv * D ? e.obs_buf[(int64_t)i0 * D + k] : 0.f;
       lds[Ld::X0 + k] = k < Rv * S ? e.share_buf[(int64_t)i0 * S + k] : 0.f;
     }
-    for (int k = tid; k < 16 * HID; k += nt) {
-      const int row = k >> 6, u = k & 63;
-      lds[Ld::hsA + row * SREC_HS + u] = row < Rv ? e.rnn_a[(int64_t)(i0 + row) * HID + u] : 0.f;
-      lds[Ld::hsC + row * SREC_HS + u] = row < Rv ? e.rnn_c[(int64_t)(i0 + row) * HID + u] : 0.f;
-    }
-    if (tid < 16) { lds[Ld::mk + tid] = tid < Rv ? e.mask_buf[i0 + tid] : 0.f; lds[Ld::act + tid] = 0.f; }
   }
-  if (wave < 4) spread_rec_role<2, TR, LN, false>(e, e.a, sh[0], lds, e.rnn_a, wave);
-  else if (wave < 7) spread_rec_role<1, TR, LN, false>(e, e.c, sh[1], lds, e.rnn_c, wave - 4);
-  else spread_rec_role<1, TR, LN, true>(e, e.c, sh[1], lds, e.rnn_c, 3);
+  if (wave < 4) spread_rec_role<2, RELU, LN, false>(e, e.a, sh[0], lds, e.rnn_a, wave);
+  else if (wave < 7) spread_rec_role<1, RELU, LN, false>(e, e.c, sh[1], lds, e.rnn_c, wave - 4);
+  else spread_rec_role<1, RELU, LN, true>(e, e.c, sh[1], lds, e.rnn_c, 3);
 }
 
 extern "C" int mappo_rollout_episode_spread_recurrent(const float *actor_params, const mappo_net_desc *actor_desc, const float *critic_params,
@@ -222,21 +190,10 @@ extern "C" int mappo_rollout_episode_spread_recurrent(const float *actor_params,
                                                       float *values, float *rnn_states, float *rnn_states_critic, int32_t centralized,
                                                       mappo_stream_t stream) {
   const char *who = "rollout_episode_spread_recurrent";
-  MAPPO_REQUIRE(actor_desc && critic_desc, "%s: bad arguments (null pointer)", who);
-  MAPPO_REQUIRE(actor_desc->recurrent && critic_desc->recurrent, "%s: needs recurrent network descriptors (actor and critic)", who);
-  if (int rc = check_desc_common(actor_desc, who)) return rc;
-  if (int rc = check_desc_common(critic_desc, who)) return rc;
-  MAPPO_REQUIRE(actor_desc->in_dim <= MAXD && critic_desc->in_dim <= MAXD, "%s: in_dim %d / %d: both networks must be narrow (<= %d)", who,
-                actor_desc->in_dim, critic_desc->in_dim, MAXD);
-  MAPPO_REQUIRE(actor_desc->layer_N <= 1 && critic_desc->layer_N <= 1, "%s: layer_N %d / %d: at most one hidden layer (layer_N <= 1)", who,
-                actor_desc->layer_N, critic_desc->layer_N);
-  MAPPO_REQUIRE(actor_desc->layer_N == critic_desc->layer_N && actor_desc->use_relu == critic_desc->use_relu,
-                "%s: actor and critic must share layer_N and the activation", who);
-  MAPPO_REQUIRE(critic_desc->out_dim == 1, "%s: critic out_dim must be 1", who);
+  if (int rc = rec_episode_check(actor_desc, critic_desc, N, M, who)) return rc;
   MAPPO_REQUIRE(actor_desc->out_dim == 5, "%s: actor out_dim %d: simple_spread has 5 actions (Discrete(5))", who, actor_desc->out_dim);
   MAPPO_REQUIRE(T >= 1 && N >= 1 && env_episode_length >= 1, "%s: bad shape T=%d N=%d env episode length %d", who, T, N, env_episode_length);
   MAPPO_REQUIRE(M >= 1 && M <= MPE_MAX_M && L >= 1 && L <= MPE_MAX_L, "%s: M=%d L=%d out of range (1 .. %d)", who, M, L, MPE_MAX_M);
-  MAPPO_REQUIRE((int64_t)N * M <= INT32_MAX / MAXD, "%s: N*M = %lld rows exceed the int32 row indices", who, (long long)N * M);
   const int D = 4 + 2 * L + 4 * (M - 1);
   MAPPO_REQUIRE(actor_desc->in_dim == D, "%s: actor in_dim %d: simple_spread with M=%d L=%d has %d observation features", who,
                 actor_desc->in_dim, M, L, D);
@@ -248,28 +205,17 @@ extern "C" int mappo_rollout_episode_spread_recurrent(const float *actor_params,
                 mask_buf && actions && logp && values && rnn_states && rnn_states_critic, "%s: bad arguments (null pointer)", who);
   MAPPO_CLEAR_STICKY();
   SpreadRecArgs e = {};
-  GruFwdArgs &a = e.a, &c = e.c;
-  a.params = actor_params; a.off = net_offsets(*actor_desc); a.desc = *actor_desc; a.L = 1; a.Nc = N * M; a.A = actor_desc->out_dim; a.head_mode = 2;
-  a.actions = actions; a.logp = logp; a.deterministic = deterministic; a.seed = seed; a.counter = counter; a.counter_dev = counter_dev;
-  c.params = critic_params; c.off = net_offsets(*critic_desc); c.desc = *critic_desc; c.L = 1; c.Nc = N * M; c.A = 1; c.head_mode = 1; c.out = values;
+  rec_episode_args(e.a, e.c, actor_params, actor_desc, critic_params, critic_desc, N * M, deterministic, seed, counter, counter_dev, actions, logp,
+                   values);
   e.env.apos = agent_pos; e.env.avel = agent_vel; e.env.lpos = landmark_pos; e.env.tstep = tstep; e.env.episode = episode;
   e.env.N = N; e.env.M = M; e.env.L = L; e.env.T = env_episode_length; e.env.mode = 1; e.env.seed = env_seed;
   e.obs_buf = obs_buf; e.share_buf = share_buf; e.rew_buf = rew_buf; e.mask_buf = mask_buf; e.rnn_a = rnn_states; e.rnn_c = rnn_states_critic;
   e.T = T; e.G = 16 / M; e.centralized = centralized;
-  const dim3 grid((unsigned)((N + e.G - 1) / e.G)), block(SREC_WAVES * WAVE);
-  hipStream_t st = as_stream(stream);
-  const bool relu = actor_desc->use_relu != 0;
-  int rc;
-  if (actor_desc->layer_N == 0) {
-    const size_t lb = sizeof(float) * SrecLds<0>::total;
-    rc = relu ? launch_kernel<rollout_episode_spread_rec_kernel<4, 0>, LDS_DYN_MAX - (int)(2 * sizeof(Step3Shared))>(who, grid, block, lb, st, e)
-              : launch_kernel<rollout_episode_spread_rec_kernel<5, 0>, LDS_DYN_MAX - (int)(2 * sizeof(Step3Shared))>(who, grid, block, lb, st, e);
-  } else {
-    const size_t lb = sizeof(float) * SrecLds<1>::total;
-    rc = relu ? launch_kernel<rollout_episode_spread_rec_kernel<4, 1>, LDS_DYN_MAX - (int)(2 * sizeof(Step3Shared))>(who, grid, block, lb, st, e)
-              : launch_kernel<rollout_episode_spread_rec_kernel<5, 1>, LDS_DYN_MAX - (int)(2 * sizeof(Step3Shared))>(who, grid, block, lb, st, e);
-  }
-  if (rc) return rc;
-  MAPPO_CHECK_LAUNCH("rollout_episode_spread_recurrent");
+  const dim3 grid((unsigned)((N + e.G - 1) / e.G)), block(REC_WAVES * WAVE);
+  if (int rc = dispatch_relu_ln<1>(actor_desc->use_relu != 0, actor_desc->layer_N, [&](auto R, auto L) {
+        return launch_kernel<rollout_episode_spread_rec_kernel<R.value, L.value>, REC_LDS_MAX>(who, grid, block, sizeof(float) * SrecLds<L.value>::total, as_stream(stream), e);
+      }))
+    return rc;
+  MAPPO_CHECK_LAUNCH(who);
   return MAPPO_OK;
 }
