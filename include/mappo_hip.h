@@ -566,6 +566,19 @@ int mappo_rollout_episode_spread_recurrent(const float *actor_params, const mapp
                                            float *mask_buf, float *actions /*[T][B]*/, float *logp /*[T][B]*/, float *values /*[T][B]*/,
                                            float *rnn_states /*[T+1][B][64]*/, float *rnn_states_critic /*[T+1][B][64]*/,
                                            int32_t centralized, mappo_stream_t stream);
+/* One launch per EVALUATION episode on the same environment (csrc/eval_spread.h; mpe_runner.py:141-183 eval: act, env.step, sum of
+ * the step rewards): only the policy acting — no critic, no buffer.  Per step t < T: actor on the observation rows of the current
+ * state with counter + t (+ *counter_dev) and row index n*M + m, argmax (deterministic) or a sample; the environments step in
+ * float64 as above, reset-on-done included.  returns [N][M]: acc = 0; acc += r_t for t = 0 .. T-1, in fp32, per row.  actions:
+ * [T][N*M] or NULL.  The five state arrays are advanced in place; nothing else is written.  Given the same parameters, state, seed
+ * and counter, the actions and the state are bit-identical to mappo_rollout_episode_spread's.
+ * Limits, each refused with a message that names it: not recurrent; in_dim <= 64 and = 4 + 2L + 4(M-1); layer_N <= 1; out_dim 5;
+ * T, N, env_episode_length >= 1; M, L in 1..8.  Validates on the host before the launch; no allocation, no host sync. */
+int mappo_eval_episode_spread(const float *actor_params, const mappo_net_desc *actor_desc /*host*/, int32_t T, int32_t N, int32_t M,
+                              int32_t L, int32_t env_episode_length, uint64_t env_seed, double *agent_pos, double *agent_vel,
+                              double *landmark_pos, int32_t *tstep, int64_t *episode, int32_t deterministic, uint64_t seed,
+                              uint64_t counter, const uint64_t *counter_dev, float *returns /*[N][M]*/, float *actions /*[T][N*M] or NULL*/,
+                              mappo_stream_t stream);
 /* One launch per rollout EPISODE of a RECURRENT shared policy on SMAC-shaped env output (csrc/rollout_smac_rec.h;
  * smac_runner.py:110-151 collect / insert over a whole episode): what mappo_recurrent_step_dual on slot 0, then for k = 1 .. T-1
  * mappo_recurrent_rollout_step (insert of env output k - 1 into slot k + the step on it), then mappo_insert_smac of env output T - 1

@@ -150,6 +150,8 @@ SIGNATURES = {
                                                _P, _I32, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
     "mappo_rollout_episode_spread_recurrent": (C.c_int, [_P, C.POINTER(NetDesc), _P, C.POINTER(NetDesc), _I32, _I32, _I32, _I32, _I32, _U64, _P,
                                                          _P, _P, _P, _P, _I32, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "mappo_eval_episode_spread": (C.c_int, [_P, C.POINTER(NetDesc), _I32, _I32, _I32, _I32, _I32, _U64, _P, _P, _P, _P, _P, _I32, _U64, _U64, _P,
+                                            _P, _P, _P]),
     "mappo_rollout_episode_smac_recurrent": (C.c_int, [_P, C.POINTER(NetDesc), _P, C.POINTER(NetDesc), _I32, _I32, _I32, _P, _P, _P, _P, _P, _P,
                                                        _I32, _U64, _U64, _P] + [_P] * 12 + [_I32, _P]),
     "mappo_mpe_reference_reset": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _U64, _P]),

@@ -246,6 +246,24 @@ class R_MAPPOPolicy:
                                    b.actions, b.action_log_probs, b.value_preds, next_values, centralized)
         return next_values
 
+    @torch.no_grad()
+    def eval_episode_env_fused(self, env_state, T, deterministic=True):
+        """A whole evaluation episode on the GPU-resident simple_spread env in one launch (mappo_eval_episode_spread): `env_state`
+        = SimpleSpreadVecEnv.episode_state().  Only the actor acts — no critic, no buffer; the env's state is left where T steps
+        leave it.  Returns the per-(env, agent) sum of the step rewards, a device tensor [N, M].  Sampling (deterministic=False)
+        draws from a counter of the evaluation's own, T per call: the training stream (actor._counter_dev, actor._sample_counter)
+        is neither read nor moved."""
+        st = env_state
+        if st["agent_pos"].device != self.device:
+            raise ValueError("eval_episode_env_fused: the env's state is not on the policy's device")
+        returns = torch.empty(st["N"], st["M"], dtype=torch.float32, device=self.device)
+        counter = getattr(self, "_eval_counter", 0)
+        self._eval_counter = counter + int(T)
+        ops.eval_episode_spread(self.actor.flat, self.actor.desc, T, st["N"], st["M"], st["L"], st["T"], st["seed"], st["agent_pos"],
+                                st["agent_vel"], st["landmark_pos"], st["tstep"], st["episode"], deterministic, self.actor._seed, counter,
+                                None, returns)
+        return returns
+
     def can_fuse_episode_recurrent(self):
         """mappo_rollout_episode_spread_recurrent: both networks recurrent with recurrent_N = 1, narrow inputs (<= 64), layer_N <= 1,
         the same trunk shape, one Categorical head."""

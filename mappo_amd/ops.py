@@ -402,6 +402,17 @@ def rollout_episode_spread_recurrent(actor_params, actor_desc, critic_params, cr
               int(bool(centralized)))
 
 
+def eval_episode_spread(actor_params, actor_desc, T, N, M, L, env_episode_length, env_seed, agent_pos, agent_vel, landmark_pos, tstep,
+                        episode, deterministic, seed, counter, counter_dev, returns, actions=None):
+    """A whole evaluation episode on the GPU-resident simple_spread env in one launch (mappo_eval_episode_spread): the actor acts
+    and the env steps T times on the five state tensors, which are advanced in place; returns [N, M] receives each row's sum of
+    the step rewards (fp32, in step order), actions [T, N*M] (optional) the chosen actions.  Nothing else is written."""
+    _env_call("mappo_eval_episode_spread", _ptr(actor_params), C.byref(actor_desc), int(T), int(N), int(M), int(L),
+              int(env_episode_length), _u64(env_seed), *_ptrs((agent_pos, agent_vel, landmark_pos, tstep, episode), _STATE_BODIES),
+              int(bool(deterministic)), _u64(seed), _u64(counter), _ptr(counter_dev, _I64, allow_none=True), _ptr(returns),
+              _ptr(actions, allow_none=True))
+
+
 def rollout_episode_smac_recurrent(actor_params, actor_desc, critic_params, critic_desc, env_obs, env_share_obs, env_avail, env_rewards,
                                    env_dones, env_bad, deterministic, seed, counter, counter_dev, obs_buf, share_buf, avail_buf, rew_buf,
                                    mask_buf, bad_mask_buf, active_mask_buf, rnn_states, rnn_states_critic, actions, logp, values, centralized):

@@ -181,10 +181,10 @@ class MPERunner(Runner):
             dev = torch.device("cuda", torch.cuda.current_device())
         return dev == self.trainer.policy.device
 
-    def _episode_state_env(self):
-        """The env steps inside the rollout kernel (SimpleSpreadVecEnv.episode_state): device state on the policy's device, no host
-        staging, and the observation / action shapes mappo_rollout_episode_spread is built for."""
-        env = self.envs
+    def _episode_state_env(self, env=None):
+        """The env (default: the training envs) steps inside the rollout kernel (SimpleSpreadVecEnv.episode_state): device state on
+        the policy's device, no host staging, and the observation / action shapes mappo_rollout_episode_spread is built for."""
+        env = self.envs if env is None else env
         if not hasattr(env, "episode_state") or self._staging is not None:
             return False
         dev = torch.device(env.device)
@@ -333,6 +333,19 @@ class MPERunner(Runner):
         envs = self.eval_envs
         if envs is None:
             return
+        policy = self.trainer.policy
+        if (os.environ.get("MAPPO_SPREAD_EVAL_EPISODE", "0") == "1" and self._episode_state_env(envs) and policy.can_fuse_episode()
+                and policy.actor.desc.layer_N <= 1):
+            # opt-in: the eval env's state lives on the device and its step is a device function — the episode (act, env step, the
+            # sum of the step rewards) is ONE launch (mappo_eval_episode_spread); the value differs from the loop's below in the
+            # last bits only (the rewards are summed per row first, then averaged)
+            envs.reset()
+            self.trainer.prep_rollout()
+            returns = policy.eval_episode_env_fused(envs.episode_state(), self.episode_length, deterministic=True)
+            info = {"eval_average_episode_rewards": [float(returns.mean())]}
+            print("eval average episode rewards of agent: " + str(info["eval_average_episode_rewards"][0]))
+            self.log_env(info, total_num_steps)
+            return
         eval_episode_rewards = []
         obs = torch.as_tensor(envs.reset(), dtype=torch.float32).to(self.device)
         N = obs.shape[0]
@@ -350,7 +363,9 @@ class MPERunner(Runner):
             obs, rewards, dones, _ = envs.step(actions_env)
             obs = torch.as_tensor(obs, dtype=torch.float32).to(self.device)
             dones_t = torch.as_tensor(dones).to(self.device).view(R)
-            eval_episode_rewards.append(torch.as_tensor(rewards, dtype=torch.float32).to(self.device))
+            rew_t = torch.as_tensor(rewards, dtype=torch.float32).to(self.device)
+            # a device env hands out its own output tensors and reuses them two steps later (SimpleSpreadVecEnv._out): keep a copy
+            eval_episode_rewards.append(rew_t.clone() if rew_t is rewards else rew_t)
             rnn_states = rnn_states * (~dones_t).view(R, 1, 1)
             masks = (~dones_t).to(torch.float32).view(R, 1)
         rew = torch.stack(eval_episode_rewards)
